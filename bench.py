@@ -7,7 +7,19 @@ same box.  No PyTorch anywhere: the GPUs are driven through libedv.so only.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--reps R] [--batch B]
                   [--total T] [--weak] [--msg-len 256] [--pipeline] [--spawn]
-                  [--no-e2e] [--no-extra] [--no-cpu-baseline]
+                  [--dump-outputs DIR]
+                  [--full [--no-e2e] [--no-extra] [--no-cpu-baseline]]
+
+A plain run does what the headline figure needs and no more: it builds the
+batch, warms up, times the K steps (with HIP events around them for the
+roofline's kernel time), writes the last step's verdicts if --dump-outputs is
+given, and prints the result line.  --full adds everything else: each kernel's
+own time (libedv_measure.so), the verdict gather and check, the one-GPU
+reference of a multi-GPU run, the host-buffer, single-call, node-path, C3-shard,
+C4, C5 and footprint legs and the libsodium CPU baseline (--no-e2e, --no-extra
+and --no-cpu-baseline take legs out of a --full run).  The C3-shard and C4
+legs time min(K, 20) steps per repetition, so a --full run stays bounded when
+K is large.
 
 A "step" = one pass of the verifier (prep + main kernels) over one batch of
 synthetic signed requests resident in HBM.
@@ -32,9 +44,10 @@ the per-rank times, gather of the accept bytes); there is no collective inside
 verification.
 
 Timing: W warm-up steps (at least --warmup-seconds of them), then R
-repetitions of exactly K steps, each bracketed by barrier + device sync; the
-max over ranks of each repetition is taken and the MEDIAN repetition is
-reported.  value = requests of all ranks / that time.  The K steps are enqueued
+repetitions (default 1, so exactly K timed steps) of exactly K steps, each
+bracketed by barrier + device sync; the max over ranks of each repetition is
+taken and the MEDIAN repetition is reported.  value = requests of all ranks /
+that time; ms_per_step = that time / K.  The K steps are enqueued
 back to back on the library stream (prep, main, prep, main, ...), so the kernel
 durations rocprofv3 reports for the run are the ones the roofline uses.
 
@@ -890,14 +903,48 @@ def c5_leg(n=20000, n_cpu=2000):
     return out
 
 
+# ------------------------------------------------------------- --dump-outputs
+DUMP_LIMIT = 64 * 10**6   # bytes a run may write under --dump-outputs, all ranks together
+DUMP_SEED = 0xD0B5
+
+
+def dump_outputs(directory, batch, rank, world):
+    """What a caller of the timed path receives from its last step: the verdict
+    byte of every request of this rank's batch, as float32 in
+    DIR/accept.npy (DIR/accept_rank<r>.npy when there are several ranks).  A
+    batch too large for DUMP_LIMIT is written as a fixed sample: the verdicts
+    at sorted positions drawn without replacement from a seeded generator."""
+    acc = batch.accept()
+    cap = (DUMP_LIMIT // world - 4096) // 4
+    if acc.size > cap:
+        acc = acc[np.sort(np.random.default_rng([DUMP_SEED, rank]).choice(acc.size, cap, replace=False))]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "accept.npy" if world == 1 else "accept_rank%d.npy" % rank),
+            acc.astype(np.float32))
+
+
 # --------------------------------------------------------------------- main
+LEG_REPS = 5    # repetitions of the C3-shard and C4 legs when --reps is not given
+LEG_STEPS = 20  # their steps per repetition at most (--steps when it is smaller): a --full run stays bounded
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5, help="untimed steps first (at least --warmup-seconds of them)")
     ap.add_argument("--warmup-seconds", type=float, default=1.0)
-    ap.add_argument("--reps", type=int, default=5, help="timed repetitions of --steps steps; the median is reported")
+    ap.add_argument("--reps", type=int, default=None,
+                    help="timed repetitions of --steps steps, the median is reported (default 1: exactly --steps "
+                         "timed steps; the C3-shard and C4 legs of --full default to %d, of min(--steps, %d) steps)"
+                         % (LEG_REPS, LEG_STEPS))
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: per-kernel times, the verdict gather and check, every leg and the CPU "
+                         "baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the verdicts of the last timed step to DIR/accept.npy "
+                         "(accept_rank<r>.npy per rank when --gpus > 1), float32, one value per request (a fixed "
+                         "seeded sample of them above %d MB)" % (DUMP_LIMIT // 10**6))
     ap.add_argument("--batch", type=int, default=65536, help="C2: requests per GPU per step")
     ap.add_argument("--total", type=int, default=0,
                     help="C3: total requests per step split by request index over the GPUs "
@@ -905,9 +952,10 @@ def parse_args():
     ap.add_argument("--weak", action="store_true", help="with --gpus > 1: C2's --batch per GPU instead of C3")
     ap.add_argument("--msg-len", type=int, default=256)
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the host-buffer boundary and node-path legs")
-    ap.add_argument("--no-extra", action="store_true", help="skip the C4 and C5 legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the libsodium CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true",
+                    help="with --full: skip the host-buffer boundary and node-path legs")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the C4 and C5 legs")
     ap.add_argument("--spawn", action="store_true", help="launch the ranks from this process even for one GPU")
     ap.add_argument("--pipeline", action="store_true",
                     help="time the two-stream pipelined submission (prep of step k+1 beside main of step k)")
@@ -974,35 +1022,43 @@ def main():
     assert np.array_equal(batch.accept(), batch.expected()), "warm-up verdicts differ from the expected ones"
 
     alone = None
-    if world > 1:
+    if world > 1 and args.full:
         # the same workload on one GPU: rank 0 times its own shard while the other
         # ranks wait at the barrier (one repetition of K steps), before the joint reps
         alone = timed_steps(step, drain, args.steps, 1, rdv, only_rank=0)[0]
+    if args.dump_outputs:
+        # no verdict of an earlier step is left where the timed steps write theirs
+        batch.d_accept.upload(np.full(n, 7, np.uint8))
     mine_s, gpu_ms = [], []
     # the kernels' GPU time inside the timed region: HIP events on the library
     # stream bracketing each repetition's steps (sequential mode: every kernel
     # of a step is on that stream)
     evs = None if args.pipeline else (StreamEvents(), s, gpu_ms)
-    reps = timed_steps(step, drain, args.steps, args.reps, rdv, own=mine_s, events=evs)
+    reps = timed_steps(step, drain, args.steps, args.reps or 1, rdv, own=mine_s, events=evs)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, batch, rank, world)
     elapsed = statistics.median(reps)
     ms_step = 1e3 * elapsed / args.steps
     value = total * args.steps / elapsed
     per_rank_s = [struct.unpack("<d", g)[0] for g in rdv.gather(struct.pack("<d", statistics.median(mine_s)))]
 
-    # the prep / main split of a launch pair (libedv_measure.so: each kernel
-    # between HIP events, on the first chunk-sized slice of this rank's batch)
     pn = min(n, 1 << 18)
     iters = max(3, min(args.steps, 10))
-    prep_ms, main_ms = edv.profile_device(batch.d_sigs.ptr, batch.d_pks.ptr, batch.d_msgs.ptr, batch.d_off.ptr, pn,
-                                          batch.d_accept.ptr, dev, iters)
-    # untimed: every rank verifies once more, packs its verdicts into a bitmask
-    # on the device (N/8 bytes), copies it D2H and sends it to rank 0, which
-    # places each shard's bits in its slice of one host array
-    batch.verify()
-    mine = batch.accept_bits()
-    parts = rdv.gather(mine.tobytes(), broadcast=False)
-    verdicts_ok = None
-    if rank == 0:
+    prep_ms = main_ms = parts = verdicts_ok = None
+    if args.full or args.pipeline:
+        # the prep / main split of a launch pair (libedv_measure.so: each kernel
+        # between HIP events, on the first chunk-sized slice of this rank's batch);
+        # a pipelined run has no other kernel time (its steps span two streams)
+        prep_ms, main_ms = edv.profile_device(batch.d_sigs.ptr, batch.d_pks.ptr, batch.d_msgs.ptr, batch.d_off.ptr, pn,
+                                              batch.d_accept.ptr, dev, iters)
+    if args.full:
+        # untimed: every rank verifies once more, packs its verdicts into a bitmask
+        # on the device (N/8 bytes), copies it D2H and sends it to rank 0, which
+        # places each shard's bits in its slice of one host array
+        batch.verify()
+        mine = batch.accept_bits()
+        parts = rdv.gather(mine.tobytes(), broadcast=False)
+    if rank == 0 and args.full:
         full = np.empty(total, np.uint8)
         bounds = ([shard.shard_range(total, world, r)[0] for r in range(world)] + [total] if c3
                   else [r * args.batch for r in range(world + 1)])
@@ -1041,9 +1097,10 @@ def main():
                 "kernel_ms_source": ("HIP events on the library stream around each timed repetition's %d steps "
                                      "(median repetition), per prep + main launch pair" % args.steps
                                      if pair_ms_timed is not None else "prep + main profile (libedv_measure.so)"),
-                "profile_pair_ms": prep_ms + main_ms,
+                "profile_pair_ms": prep_ms + main_ms if prep_ms is not None else None,
                 "profile_what": "prep_kernel_ms / main_kernel_ms: each kernel alone between HIP events "
-                                "(libedv_measure.so, %d launch pairs, a sync after each)" % iters,
+                                "(libedv_measure.so, %d launch pairs, a sync after each)" % iters
+                                if prep_ms is not None else "not measured (--full measures it)",
                 "vop2_issue_peak": PEAK_VOP2 / 1e12,
                 "convention": "achieved = SURVEY 8d W(m) INT32 ops per verify x verifies per launch pair / the pair's "
                               "GPU time; peak = 256 CU x 64 lanes x 2.4 GHz (4-cycle VOP3 issue)"}
@@ -1052,25 +1109,26 @@ def main():
         if "dram_bytes_per_verify_upper_bound" in pmc:
             roofline["dram_frac_of_hbm_peak_upper_bound"] = pmc["dram_bytes_per_verify_upper_bound"] * value / PEAK_HBM
     if world > 1:
-        one_gpu = n * args.steps / alone   # rank 0's shard, timed alone
         out_multi = {"per_gpu_verifies_per_s": value / world,
                      "per_rank_s": per_rank_s, "slowest_rank": int(np.argmax(per_rank_s)),
                      "slowest_rank_s": max(per_rank_s), "per_rank_what": "each rank's median repetition "
                      "(%d steps), its own clock between the barriers" % args.steps,
-                     "one_gpu_same_workload_verifies_per_s": one_gpu,
-                     "one_gpu_same_workload_what": "rank 0's shard (%d requests per step) timed alone, %d steps, the "
-                                                   "other ranks idle at a barrier, before the joint repetitions"
-                                                   % (n, args.steps),
-                     "gathered_bytes": gathered_bytes,
-                     "gathered": "accept bitmask, %d bytes from %d ranks (packed on each GPU, D2H, loopback TCP to "
-                                 "rank 0, after the timed region)" % (gathered_bytes, world),
+                     **({"one_gpu_same_workload_verifies_per_s": n * args.steps / alone,   # rank 0's shard, alone
+                         "one_gpu_same_workload_what": "rank 0's shard (%d requests per step) timed alone, %d steps, "
+                                                       "the other ranks idle at a barrier, before the joint "
+                                                       "repetitions" % (n, args.steps),
+                         "gathered_bytes": gathered_bytes,
+                         "gathered": "accept bitmask, %d bytes from %d ranks (packed on each GPU, D2H, loopback TCP "
+                                     "to rank 0, after the timed region)" % (gathered_bytes, world)}
+                        if args.full else {}),
                      "gpu_isolation": ("HIP_VISIBLE_DEVICES=<the LOCAL_RANK-th device> per rank" if own_gpu is not None
                                        else "EDV_VIRTUAL_DEVICES=%s: logical devices sharing the visible GPU(s) "
                                             "(rehearsal)" % os.environ.get("EDV_VIRTUAL_DEVICES"))}
     if c3:
         config = {"workload": "C3: %d Ed25519 verifies per step split by request index over %d GPU(s) (%d per GPU), "
-                              "fixed %d-byte serialized requests, 5 %% invalid, accept bitmask gathered to host and "
-                              "checked" % (total, world, n, args.msg_len),
+                              "fixed %d-byte serialized requests, 5 %% invalid%s"
+                              % (total, world, n, args.msg_len,
+                                 ", accept bitmask gathered to host and checked" if args.full else ""),
                   "total_per_step": total, "per_gpu": n, "msg_len": args.msg_len,
                   "parallelism": "shard-by-request-index x%d (one process per GPU)" % world}
     else:
@@ -1107,7 +1165,8 @@ def main():
                              ("torch.distributed.run ranks" if world > 1 else "single process"),
                    "input_generation_s": t_gen},
     }
-    if world == 1 and not c3 and not args.no_e2e:
+    legs = args.full and world == 1 and not c3   # the legs beside the headline are C2's, on one GPU
+    if legs and not args.no_e2e:
         out["e2e"] = e2e_leg(batch, value)
         out["boundary_async_pinned_vs_headline"] = out["e2e"]["async_pinned_vs_device_resident"]
         try:
@@ -1118,19 +1177,21 @@ def main():
             out["node_path"] = node_path_leg()
         except Exception as ex:
             out["node_path"] = {"error": repr(ex)}
-    if world == 1 and not c3 and not args.no_extra:
-        for name, leg in (("c3_shard", lambda: c3_shard_leg(dev, args.steps, args.reps)),
-                          ("c4", lambda: c4_leg(dev, args.steps, args.reps)), ("c5", c5_leg)):
+    if legs and not args.no_extra:
+        # the legs keep the step count they were sized for however long the headline runs
+        leg_steps, leg_reps = min(args.steps, LEG_STEPS), args.reps or LEG_REPS
+        for name, leg in (("c3_shard", lambda: c3_shard_leg(dev, leg_steps, leg_reps)),
+                          ("c4", lambda: c4_leg(dev, leg_steps, leg_reps)), ("c5", c5_leg)):
             try:
                 out[name] = leg()
             except Exception as ex:
                 out[name] = {"error": repr(ex)}
-    if world == 1 and not c3 and not args.no_e2e:
+    if legs and not args.no_e2e:
         try:
             out["footprint"] = footprint_leg(batch, dev)
         except Exception as ex:
             out["footprint"] = {"error": repr(ex)}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         # rank 0, after the timed region and the gather (the other ranks have
         # left), on a bounded sample of the requests the GPUs verified: the
         # whole C2 batch, or the first CPU_SAMPLE requests of rank 0's C3 shard

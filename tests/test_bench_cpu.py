@@ -104,6 +104,42 @@ def test_bench_imports_no_torch():
     assert json.loads(r.stdout.strip()) is False
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: a rank's verdict bytes as float32, whole while they fit
+    the byte limit (split evenly over the ranks), else a sample at sorted,
+    distinct positions that depend on the rank and sizes only; the files of all
+    ranks stay within the limit."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class Batch:
+        def __init__(self, n):
+            self.a = (np.arange(n) % 20 != 10).astype(np.uint8)
+
+        def accept(self):
+            return self.a
+
+    b = Batch(TOTAL)
+    bench.dump_outputs(str(tmp_path / "whole"), b, 0, 1)
+    got = np.load(tmp_path / "whole" / "accept.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, b.a)
+    assert TOTAL * 4 < bench.DUMP_LIMIT <= 64 * 10**6
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 200000)
+    for run in ("s1", "s2"):
+        for rank in range(2):
+            bench.dump_outputs(str(tmp_path / run), b, rank, 2)
+    files = sorted(os.listdir(tmp_path / "s1"))
+    assert files == ["accept_rank0.npy", "accept_rank1.npy"]
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in files) <= 200000
+    for f in files:
+        s1 = np.load(tmp_path / "s1" / f)
+        assert s1.dtype == np.float32 and s1.size == (100000 - 4096) // 4
+        assert np.array_equal(s1, np.load(tmp_path / "s2" / f))
+        assert abs(s1.mean() - 0.95) < 0.01            # the damaged twentieth, sampled
+    idx = np.sort(np.random.default_rng([bench.DUMP_SEED, 1]).choice(TOTAL, (100000 - 4096) // 4, replace=False))
+    assert np.array_equal(np.load(tmp_path / "s1" / "accept_rank1.npy"), b.a[idx])
+
+
 @pytest.mark.parametrize("vis,local,world,want", [
     (None, 3, 8, (0, "3")), ("4,5,6,7", 2, 4, (0, "6")), (" 0 , 1", 1, 2, (0, "1")),
     ("", 1, 2, (1, None)), ("0", 0, 1, (0, None))])

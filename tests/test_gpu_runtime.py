@@ -614,16 +614,16 @@ def _bench(args, env=None, launcher=None, timeout=420):
     return json.loads(lines[0])
 
 
-_QUICK = ["--steps", "2", "--reps", "2", "--warmup", "1", "--warmup-seconds", "0", "--no-cpu-baseline"]
+_QUICK = ["--full", "--steps", "2", "--reps", "2", "--warmup", "1", "--warmup-seconds", "0", "--no-cpu-baseline"]
 
 
 def test_bench_default_line_contract():
-    """The N = 1 line the driver reads (C2, legs off): the contract's keys, the
+    """The N = 1 line of a --full run (C2, legs off): the contract's keys, the
     roofline object (bound, achieved = W ops / kernel time, peak, unit, frac =
     achieved / peak, traffic from the PMC summary while the kernel sources match
     it, else null) and the CPU baseline object with its sample and thread count."""
     import bench
-    line = _bench(["--steps", "3", "--reps", "2", "--warmup", "1", "--warmup-seconds", "0", "--no-e2e",
+    line = _bench(["--full", "--steps", "3", "--reps", "2", "--warmup", "1", "--warmup-seconds", "0", "--no-e2e",
                    "--no-extra"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
               "scaling", "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
@@ -647,6 +647,35 @@ def test_bench_default_line_contract():
     cb = line["cpu_baseline"]
     assert cb["kind"] in ("reference", "port") and cb["value"] > 0 and cb["cores"] >= 1 and cb["sample"]
     assert 0 < rf["job_frac"] <= 1 and rf["rank0_kernel_frac"] == rf["frac"]
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """The plain line (no --full): exactly --steps timed steps in one
+    repetition, the headline keys with the roofline from the HIP events around
+    those steps, and nothing that takes a run of its own (per-kernel profile,
+    verdict gather, legs, CPU baseline).  --dump-outputs writes the verdicts of
+    the last timed step: float32, one per request, all 1 (C2 is all valid), and
+    for C3 (5 % damaged at known positions) equal to the construction."""
+    from indy_plenum_amd import workload
+    d = tmp_path / "c2"
+    line = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--warmup-seconds", "0", "--dump-outputs", str(d)])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 3 and line["timing"]["median_of"] == 1 and line["timing"]["warmup_steps_run"] == 1
+    assert abs(line["value"] - 65536 / (line["ms_per_step"] * 1e-3)) / line["value"] < 1e-9
+    rf = line["roofline"]
+    assert rf["kernel_ms_source"].startswith("HIP events") and 0 < rf["frac"] <= 1
+    assert rf["prep_kernel_ms"] is None and rf["main_kernel_ms"] is None and line["verdicts_as_expected"] is None
+    for k in ("cpu_baseline", "e2e", "single_call", "node_path", "c3_shard", "c4", "c5", "footprint"):
+        assert k not in line, k
+    assert sorted(os.listdir(d)) == ["accept.npy"]
+    acc = np.load(d / "accept.npy")
+    assert acc.dtype == np.float32 and acc.shape == (65536,) and np.all(acc == 1.0)
+    exp = np.ones(131072, np.float32)
+    exp[workload.damage_positions(0, 131072, 20)] = 0
+    _bench(["--total", "131072", "--steps", "1", "--warmup", "1", "--warmup-seconds", "0",
+            "--dump-outputs", str(tmp_path / "c3")])
+    assert np.array_equal(np.load(tmp_path / "c3" / "accept.npy"), exp)
 
 
 def test_bench_c3_mode_bounded():
@@ -720,8 +749,8 @@ def test_bench_c3_full_size_virtual_ranks(ranks):
     construction (5 % damaged at known positions)."""
     env = dict(os.environ, EDV_VIRTUAL_DEVICES=str(ranks))
     env.pop("WORLD_SIZE", None)
-    line = _bench(["--gpus", str(ranks), "--steps", "2", "--reps", "1", "--warmup", "1", "--warmup-seconds", "0",
-                   "--cpu-seconds", "3"], env=env, timeout=900)
+    line = _bench(["--gpus", str(ranks), "--full", "--steps", "2", "--reps", "1", "--warmup", "1",
+                   "--warmup-seconds", "0", "--cpu-seconds", "3"], env=env, timeout=900)
     assert line["n_gpus"] == ranks and line["verdicts_as_expected"] is True
     assert line["config"]["total_per_step"] == 16777216 and line["config"]["per_gpu"] == 16777216 // ranks
     mg = line["multi_gpu"]

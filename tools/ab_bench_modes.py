@@ -20,7 +20,8 @@ if __name__ == "__main__":
     extra = [x for x in extra if x != "--"]
     for _ in range(a.rounds):
         for m in a.modes.split("|"):
-            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-e2e", "--no-extra", "--no-cpu-baseline"]
+            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-e2e", "--no-extra",
+                   "--no-cpu-baseline"]
             cmd += m.split() + extra
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
             if r.returncode != 0:

@@ -1,7 +1,7 @@
 #!/bin/bash
 # One GPU-box session (round 6).  STEP picks the parts (comma list):
 #   test    pytest -m gpu + smoke()            (PYTEST_ARGS narrows it)
-#   bench   the default bench.py line           (BENCH_ARGS)
+#   bench   the bench.py --full line            (BENCH_ARGS)
 #   trace   anatomy of synchronous C2 calls (kernel + copy + HIP API traces)
 #   gather  PMC passes over tools/ubench_gather (counter calibration, known bytes)
 #   flush   C2 launch pair with / without an Infinity-Cache flush between prep and main
@@ -74,7 +74,7 @@ if has flush; then
 fi
 if has bench; then
   log bench
-  timeout -k 10 900 python3 bench.py $BENCH_ARGS > $O/bench.json 2> $O/bench.err || fail bench $O/bench.err
+  timeout -k 10 900 python3 bench.py --full $BENCH_ARGS > $O/bench.json 2> $O/bench.err || fail bench $O/bench.err
   cat $O/bench.json
 fi
 if has prof; then
