@@ -9,6 +9,7 @@
 #include "edv_verify_core.h"
 #include "edv_sha256.h"
 #include "edv_ledger.h"
+#include "edv_probe_ops.h"
 
 using namespace edv;
 
@@ -179,6 +180,78 @@ int hc_half_scalars(const uint8_t* h32, uint8_t* a32, uint8_t* u32) {
   store_words(a32, a, 8);
   store_words(u32, u, 8);
   return neg ? 1 : 0;
+}
+// The one-lane math probes of include/edv_measure.h on the CPU build of the
+// headers: edv_probe_math's ops and packed layout (edv_probe_ops.h), so the
+// tests run one set of cases through both builds.  -1: not a one-lane op, or
+// strides below the op's sizes.
+int hc_probe_math(int op, const void* in, uint64_t in_stride, void* out, uint64_t out_stride, uint64_t n) {
+  const ProbeSize sz = probe_size(op);
+  if (!sz.in || probe_is_quad(op) || in_stride < sz.in || out_stride < sz.out || (in_stride & 3) || (out_stride & 3))
+    return -1;
+  for (uint64_t i = 0; i < n; i++) {
+    const uint32_t* x = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(in) + i * in_stride);
+    uint32_t* y = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(out) + i * out_stride);
+    switch (op) {
+#define HC_PROBE_CASE(OP) case OP: probe_lane_op<OP>(x, y); break;
+      HC_PROBE_CASE(EDV_PROBE_FE_MUL)
+      HC_PROBE_CASE(EDV_PROBE_FE_SQ)
+      HC_PROBE_CASE(EDV_PROBE_FE_SQ2)
+      HC_PROBE_CASE(EDV_PROBE_FE_SQ_FLOOR)
+      HC_PROBE_CASE(EDV_PROBE_FE_TOBYTES)
+      HC_PROBE_CASE(EDV_PROBE_FE_FROMBYTES)
+      HC_PROBE_CASE(EDV_PROBE_FE_INVERT_SAFEGCD)
+      HC_PROBE_CASE(EDV_PROBE_FE_POW22523)
+      HC_PROBE_CASE(EDV_PROBE_SC_REDUCE)
+      HC_PROBE_CASE(EDV_PROBE_HALF_SCALARS)
+      HC_PROBE_CASE(EDV_PROBE_RECODE5)
+      HC_PROBE_CASE(EDV_PROBE_APPROX_DIV)
+      HC_PROBE_CASE(EDV_PROBE_FDIV_FLOOR)
+      HC_PROBE_CASE(EDV_PROBE_EUCLID_DIV)
+      HC_PROBE_CASE(EDV_PROBE_GE_FROMBYTES)
+#undef HC_PROBE_CASE
+      default: return -1;
+    }
+  }
+  return 0;
+}
+// single-case forms of the ops the harness had no entry point for
+double hc_approx_div(double a, double b) { return approx_div(a, b); }
+double hc_fdiv_floor(double a, double b) { return fdiv_floor(a, b); }
+// r0, t0 <- one Euclidean step against r1, t1 (8 words each, in place)
+void hc_euclid_div(uint32_t* r0, uint32_t* t0, const uint32_t* r1, const uint32_t* t1) { euclid_div(r0, t0, r1, t1); }
+// recode5 digits of a 32-byte scalar < 2^253; returns digits5_windows of them
+int hc_recode5_windows(const uint8_t* in32, uint32_t* out8) {
+  uint32_t w[8];
+  load_words(w, in32, 8);
+  recode5(out8, w);
+  return digits5_windows(out8);
+}
+// ge_frombytes_negate's point as limbs (X Y Z T); returns ge_is_canonical |
+// has_small_order << 1 | ge_frombytes_negate << 2
+int hc_ge_frombytes_negate_limbs(const uint8_t* in32, int32_t* out40) {
+  uint32_t w[8];
+  load_words(w, in32, 8);
+  ge_p3 p;
+  const bool ok = ge_frombytes_negate(p, w);
+  from_fe(out40, p.X);
+  from_fe(out40 + 10, p.Y);
+  from_fe(out40 + 20, p.Z);
+  from_fe(out40 + 30, p.T);
+  return int(ge_is_canonical(w)) | int(has_small_order(w)) << 1 | int(ok) << 2;
+}
+// plain (one-lane) group arithmetic on limb vectors, the CPU check of the quad
+// formulas' references: p3 = X Y Z T (40 limbs)
+void hc_ge_add_p3(const int32_t* p40, const int32_t* q40, int32_t* out40) {
+  const ge_p3 p{to_fe(p40), to_fe(p40 + 10), to_fe(p40 + 20), to_fe(p40 + 30)};
+  const ge_p3 q{to_fe(q40), to_fe(q40 + 10), to_fe(q40 + 20), to_fe(q40 + 30)};
+  const ge_p3 r = ge_p1p1_to_p3(ge_add(p, ge_p3_to_cached(q)));
+  from_fe(out40, r.X); from_fe(out40 + 10, r.Y); from_fe(out40 + 20, r.Z); from_fe(out40 + 30, r.T);
+}
+void hc_ge_dbl_p3(const int32_t* p40, int32_t* out40) {
+  const ge_p3 p{to_fe(p40), to_fe(p40 + 10), to_fe(p40 + 20), to_fe(p40 + 30)};
+  const ge_p3 r = ge_p1p1_to_p3(ge_p2_dbl(ge_p3_to_p2(p)));
+  from_fe(out40, r.X); from_fe(out40 + 10, r.Y); from_fe(out40 + 20, r.Z); from_fe(out40 + 30, r.T);
 }
 // the walk's layout constants: kAWin, kAEntries, kBBits, kBTables
 void hc_layout(int32_t* out4) {

@@ -1,10 +1,11 @@
 // edv_measure.inc -- the measurement entry points of libedv_measure.so
 // (include/edv_measure.h): kernel timing on the kernels' own stream, the
-// Infinity-Cache flush probe, the prep kernel's sides timed apart, and the
-// asynchronous path's fault hook.  Included at the end of edv_runtime.hip only
+// Infinity-Cache flush probe, the prep kernel's sides timed apart, the
+// asynchronous path's fault hook and the device math probes.  Included at the end of edv_runtime.hip only
 // when EDV_MEASUREMENT_API is defined (the Makefile's libedv_measure.so); the
 // product libedv.so has none of it.
 #include "../../include/edv_measure.h"
+#include "edv_probe.h"
 
 namespace {
 
@@ -180,6 +181,38 @@ int edv_test_fail_async(int device, int64_t ticket) {
   CtxLock cl(device);
   if (cl.err) return cl.err;
   cl.c->inject_fail = ticket;
+  return 0;
+}
+
+int edv_probe_math(int device, int op, const void* in, uint64_t in_stride, void* out, uint64_t out_stride,
+                   uint64_t n) {
+  g_err.clear();
+  const ProbeSize sz = probe_size(op);
+  if (!sz.in) return set_err(EDV_E_ARG, "probe: unknown op");
+  if (!in || !out) return set_err(EDV_E_ARG, "probe: null buffer");
+  if (in_stride < sz.in || out_stride < sz.out || (in_stride & 3) || (out_stride & 3) || in_stride > 4096 ||
+      out_stride > 4096)
+    return set_err(EDV_E_ARG, "probe: strides are multiples of 4, from the op's sizes up to 4096");
+  if (n > (uint64_t(1) << 24)) return set_err(EDV_E_ARG, "probe: at most 2^24 cases");
+  if (n == 0) return 0;
+  CtxLock cl(device);
+  if (cl.err) return cl.err;
+  DevCtx* c = cl.c;
+  // the two buffers live for this call only
+  struct ProbeBuf : DevBuf {
+    ~ProbeBuf() {
+      if (p) (void)hipFree(p);
+    }
+  } din, dout;
+  if (din.ensure(n * in_stride) || dout.ensure(n * out_stride)) return EDV_E_OOM;
+  HIPOK(hipMemcpyAsync(din.p, in, n * in_stride, hipMemcpyHostToDevice, c->stream), "probe copy in");
+  HIPOK(hipMemsetAsync(dout.p, 0, n * out_stride, c->stream), "probe memset");
+  HIPOK((probe_is_quad(op) ? launch_probe_quad : launch_probe_lane)(c->stream, op, static_cast<const uint8_t*>(din.p),
+                                                                    in_stride, static_cast<uint8_t*>(dout.p),
+                                                                    out_stride, n),
+        "probe launch");
+  HIPOK(hipMemcpyAsync(out, dout.p, n * out_stride, hipMemcpyDeviceToHost, c->stream), "probe copy out");
+  HIPOK(hipStreamSynchronize(c->stream), "probe sync");  // the buffers are freed on return
   return 0;
 }
 

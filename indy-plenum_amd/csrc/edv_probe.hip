@@ -1,0 +1,53 @@
+// edv_probe.hip -- TESTS ONLY, libedv_measure.so only: the one-lane math
+// probes (include/edv_measure.h edv_probe_math).  One lane runs one case of
+// edv_probe_ops.h's probe_lane_op, which calls the header function unchanged;
+// compiled like the batch path's main kernel (edv_verify.hip), with the field
+// arithmetic's scheduling fences.  Straight-line code and loops with fixed
+// bounds only.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "edv_probe.h"
+
+namespace edv {
+namespace {
+
+template <int OP>
+__global__ __launch_bounds__(256) void edv_probe_lane_kernel(const uint8_t* in, uint64_t in_stride, uint8_t* out,
+                                                             uint64_t out_stride, uint64_t n) {
+  const uint64_t i = uint64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= n) return;
+  probe_lane_op<OP>(reinterpret_cast<const uint32_t*>(in + i * in_stride),
+                    reinterpret_cast<uint32_t*>(out + i * out_stride));
+}
+
+}  // namespace
+
+hipError_t launch_probe_lane(hipStream_t s, int op, const uint8_t* in, uint64_t in_stride, uint8_t* out,
+                             uint64_t out_stride, uint64_t n) {
+  const dim3 grid(unsigned((n + 255) / 256)), block(256);
+  switch (op) {
+#define EDV_PROBE_CASE(OP) \
+  case OP: edv_probe_lane_kernel<OP><<<grid, block, 0, s>>>(in, in_stride, out, out_stride, n); break;
+    EDV_PROBE_CASE(EDV_PROBE_FE_MUL)
+    EDV_PROBE_CASE(EDV_PROBE_FE_SQ)
+    EDV_PROBE_CASE(EDV_PROBE_FE_SQ2)
+    EDV_PROBE_CASE(EDV_PROBE_FE_SQ_FLOOR)
+    EDV_PROBE_CASE(EDV_PROBE_FE_TOBYTES)
+    EDV_PROBE_CASE(EDV_PROBE_FE_FROMBYTES)
+    EDV_PROBE_CASE(EDV_PROBE_FE_INVERT_SAFEGCD)
+    EDV_PROBE_CASE(EDV_PROBE_FE_POW22523)
+    EDV_PROBE_CASE(EDV_PROBE_SC_REDUCE)
+    EDV_PROBE_CASE(EDV_PROBE_HALF_SCALARS)
+    EDV_PROBE_CASE(EDV_PROBE_RECODE5)
+    EDV_PROBE_CASE(EDV_PROBE_APPROX_DIV)
+    EDV_PROBE_CASE(EDV_PROBE_FDIV_FLOOR)
+    EDV_PROBE_CASE(EDV_PROBE_EUCLID_DIV)
+    EDV_PROBE_CASE(EDV_PROBE_GE_FROMBYTES)
+#undef EDV_PROBE_CASE
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+}  // namespace edv

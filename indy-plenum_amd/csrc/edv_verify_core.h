@@ -307,10 +307,12 @@ EDV_HD void w8_shr1(uint32_t a[8]) {
   a[7] >>= 1;
 }
 
-// a / b to about 2^-50 relative.  On the GPU: v_rcp_f64 and one Newton step
-// (4 instructions) in place of the IEEE-exact division sequence (div_scale x 2,
-// rcp, five fma, div_fmas, div_fixup); every caller corrects its quotient
-// afterwards, so exactness is not needed (see fdiv_floor and euclid_div).
+// a / b to within 2^-48.7 relative (measured on MI355X against exact rationals:
+// tests/test_gpu_math_device.py, which asserts the 2^-45 that euclid_div
+// needs).  On the GPU: v_rcp_f64 and one Newton step (4 instructions) in place
+// of the IEEE-exact division sequence (div_scale x 2, rcp, five fma, div_fmas,
+// div_fixup); every caller corrects its quotient afterwards, so exactness is
+// not needed (see fdiv_floor and euclid_div).
 #ifndef EDV_RCP_DIV
 #define EDV_RCP_DIV 1
 #endif
@@ -346,12 +348,16 @@ EDV_HD void euclid_div(uint32_t r0[8], uint32_t t0[8], const uint32_t r1[8], con
       br = s >> 32;
     }
   } else {
-    // binary long division over quotient bits e..0, 2^e <= qd <= q: r1 << e
-    // stays below r0, so nothing overflows
+    // binary long division over quotient bits e..0.  The top bit comes from
+    // the estimate scaled back UP: qd may fall below a power of two that q
+    // reaches (q = 2^127 + 1 read as 2^127 - 1 left the remainder above r1),
+    // while qd (1 + 2^-42) >= q - 1, so with the final correction no quotient
+    // bit is missed; 2^e <= q (1 + 2^-42), so r1 << e stays below 2^256 for
+    // r0 <= 8L (at most one leading step subtracts nothing)
     uint32_t d[8], v[8];
 #pragma unroll
     for (int i = 0; i < 8; i++) { d[i] = r1[i]; v[i] = t1[i]; }
-    const int e = int((__builtin_bit_cast(uint64_t, qd) >> 52) & 0x7ff) - 1023;  // floor(log2 qd), qd >= 2^31
+    const int e = int((__builtin_bit_cast(uint64_t, qd * (1.0 + 0x1p-42)) >> 52) & 0x7ff) - 1023;  // qd >= 2^31
 #pragma unroll 1
     for (int k = 0; k < e; k++) { w8_shl1(d); w8_shl1(v); }
 #pragma unroll 1
@@ -404,9 +410,11 @@ EDV_HD double w8_window53(const uint32_t r[8], int s) {
   return double(v);
 }
 // floor(a / b) for exact non-negative integers a < 2^54, 0 < b < 2^54 in doubles:
-// exact whenever the quotient is below 2^50 (the estimate is then within one
-// of it and the remainder test fixes that); larger quotients may be off, and
-// every caller rejects a quotient that large (Lehmer: cofactor above 2^30).
+// exact whenever the quotient is below 2^48 (approx_div's measured error keeps
+// the estimate within one of it and the remainder test fixes that; the device
+// test asserts it below 2^45 and saw no wrong quotient up to 2^52); larger
+// quotients may be off, and every caller rejects a quotient that large
+// (Lehmer: cofactor above 2^30).
 EDV_HD double fdiv_floor(double a, double b) {
   double q = __builtin_floor(approx_div(a, b));
   const double r = __builtin_fma(-q, b, a);

@@ -163,6 +163,7 @@ def measure_lib():
                                                   f32p, f32p, f32p]
         h.edv_profile_prep_sides.argtypes = [vp, vp, vp, vp, u64, u64, vp, ctypes.c_int, ctypes.c_int, f32p]
         h.edv_test_fail_async.argtypes = [ctypes.c_int, ctypes.c_int64]
+        h.edv_probe_math.argtypes = [ctypes.c_int, ctypes.c_int, vp, u64, vp, u64, u64]
         h.edv_verify_batch_async.argtypes = [vp, vp, vp, vp, u64, vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]
         h.edv_wait_async.argtypes = [ctypes.c_int, ctypes.c_int64]
         h.edv_last_error.restype = ctypes.c_char_p
@@ -620,3 +621,28 @@ def profile_prep_sides(d_sigs, d_pks, d_msgs, d_off, n, d_accept, device=0, iter
     _mcheck(measure_lib().edv_profile_prep_sides(d_sigs, d_pks, d_msgs, d_off, msg_base, n, d_accept, device, iters,
                                                  ms))
     return dict(zip(PREP_SIDE_KEYS, (float(x) for x in ms)))
+
+
+# op codes and (input, output) bytes per case of edv_probe_math (include/edv_measure.h)
+PROBE_OPS = {
+    "fe_mul": (1, 80, 40), "fe_sq": (2, 40, 40), "fe_sq2": (3, 40, 40), "fe_sq_floor": (4, 40, 40),
+    "fe_tobytes": (5, 40, 32), "fe_frombytes": (6, 32, 40), "fe_invert_safegcd": (7, 40, 40),
+    "fe_pow22523": (8, 40, 40), "sc_reduce": (9, 64, 32), "half_scalars": (10, 32, 68), "recode5": (11, 32, 36),
+    "approx_div": (12, 16, 8), "fdiv_floor": (13, 16, 8), "euclid_div": (14, 128, 64),
+    "ge_frombytes": (15, 32, 172), "quad_sq_shift": (16, 176, 160), "quad_dbl": (17, 160, 160),
+    "quad_add": (18, 320, 160), "quad_cached": (19, 160, 160), "quad_cached_signed": (20, 164, 160),
+}
+
+
+def probe_math(op, cases, device=0):
+    """Runs the device build of one header function on packed cases
+    (edv_probe_math): `cases` is a C-contiguous uint8 array (n, input bytes of
+    `op`); returns a uint8 array (n, output bytes)."""
+    code, nin, nout = PROBE_OPS[op]
+    cases = np.ascontiguousarray(cases, dtype=np.uint8)
+    if cases.ndim != 2 or cases.shape[1] != nin:
+        raise ValueError("probe {}: cases must be (n, {}) bytes".format(op, nin))
+    out = np.zeros((cases.shape[0], nout), np.uint8)
+    _mcheck(measure_lib().edv_probe_math(device, code, cases.ctypes.data, nin, out.ctypes.data, nout,
+                                         cases.shape[0]))
+    return out

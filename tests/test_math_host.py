@@ -10,43 +10,25 @@ import pytest
 import golden_io
 import hostcheck_lib
 
-P = 2**255 - 19
-L = 2**252 + 27742317777372353535851937790883648493
-POS = [0, 26, 51, 77, 102, 128, 153, 179, 204, 230]
-# input bound the multiply is specified for: |f_i| <= 1.65 * 2^26 (even i), 1.65 * 2^25 (odd i)
-BOUND = [int(1.65 * 2**26) if i % 2 == 0 else int(1.65 * 2**25) for i in range(10)]
-
-
-def val(l):
-    return sum(int(x) << POS[i] for i, x in enumerate(l))
+# the case generators and helpers are shared with the device-side probes
+# (test_math_reference_cpu.py, test_gpu_math_device.py)
+from math_cases import (BOUND, L, N8L, P, POS, digits_windows_cases, fe_bytes_values, fe_invert_cases,  # noqa: F401
+                        fe_mul_sq_cases, fe_sq_floor_starts, half_scalars_values, limbs, out_ok, rand_limbs,
+                        recoding_values, sc_reduce_values, val)
+from math_cases import ed_add as _ed_add, ed_decode as _ed_decode, ed_encode as _ed_encode
+from math_cases import signed_digits as _digits
 
 
 def arr(l):
     return (ctypes.c_int32 * 10)(*l)
 
 
-def limbs(x):
-    return [(x >> POS[i]) & ((1 << (26 if i % 2 == 0 else 25)) - 1) for i in range(10)]
-
-
-def rand_limbs(r, extreme=False):
-    if extreme:
-        return [r.choice([-BOUND[i], BOUND[i], BOUND[i] - 1, -BOUND[i] + 1]) for i in range(10)]
-    return [r.randrange(-BOUND[i], BOUND[i] + 1) for i in range(10)]
-
-
-def out_ok(h):
-    # outputs must be reduced enough to feed another multiply after one add/sub
-    return all(abs(h[i]) <= (2**25 + 2**20 if i % 2 == 0 else 2**24 + 2**20) for i in range(10))
-
-
 def test_fe_mul_sq_against_python():
     hc = hostcheck_lib.load()
-    r = random.Random(5)
     h = (ctypes.c_int32 * 10)()
-    for it in range(3000):
-        f = rand_limbs(r, extreme=(it % 3 == 0))
-        g = rand_limbs(r, extreme=(it % 5 == 0))
+    cases = fe_mul_sq_cases()
+    assert len(cases) == 3000
+    for f, g in cases:
         hc.hc_fe_mul(arr(f), arr(g), h)
         assert val(h) % P == val(f) * val(g) % P and out_ok(h)
         hc.hc_fe_sq(arr(f), h)
@@ -62,13 +44,9 @@ def test_fe_sq_floor_chain():
     [0, 2^25) (h1 within 2^17), so the next squaring's premultiplied operands
     stay inside int32."""
     hc = hostcheck_lib.load()
-    r = random.Random(9)
     h = (ctypes.c_int32 * 10)()
-    top = [(1 << 26) - 1 if i % 2 == 0 else (1 << 25) - 1 for i in range(10)]
-    starts = [[r.randrange(-2**25, 2**25) if i % 2 == 0 else r.randrange(-2**24, 2**24) for i in range(10)]
-              for _ in range(300)]
-    starts += [[(2**25 if i % 2 == 0 else 2**24) * s for i in range(10)] for s in (1, -1)]
-    starts += [top, [t if i != 1 else (1 << 25) + (1 << 17) for i, t in enumerate(top)]]
+    starts = fe_sq_floor_starts()
+    assert len(starts) == 304
     for f in starts:
         x = val(f) % P
         cur = f
@@ -85,15 +63,8 @@ def test_digits_windows():
     """The window count from the packed 4-bit digits (count-leading-zeros form)
     is 1 + the index of the top nonzero digit, 0 for no digits."""
     hc = hostcheck_lib.load()
-    r = random.Random(11)
-    cases = [[0] * 8, [1] + [0] * 7, [0] * 7 + [0xF0000000], [0] * 7 + [1], [0x80000000] + [0] * 7]
-    for _ in range(3000):
-        w = [0] * 8
-        top = r.randrange(64)
-        for k in range(top + 1):
-            w[k // 8] |= r.randrange(16) << (4 * (k % 8))
-        w[top // 8] |= r.randrange(1, 16) << (4 * (top % 8))
-        cases.append(w)
+    cases = digits_windows_cases()
+    assert len(cases) == 3005
     for w in cases:
         digits = [(w[k // 8] >> (4 * (k % 8))) & 15 for k in range(64)]
         want = max([k + 1 for k in range(64) if digits[k]], default=0)
@@ -102,18 +73,17 @@ def test_digits_windows():
 
 def test_fe_tobytes_canonical_and_frombytes():
     hc = hostcheck_lib.load()
-    r = random.Random(6)
     out = ctypes.create_string_buffer(32)
     h = (ctypes.c_int32 * 10)()
-    specials = [0, 1, P - 1, P, P + 1, 2 * P - 1, 2**255 - 1, 2**255 - 20, 19, 2**255 - 19 - 1]
-    for x in specials + [r.randrange(2**255) for _ in range(2000)]:
+    xs, noncanon = fe_bytes_values()
+    assert len(xs) == 2010 and len(noncanon) == 2000
+    for x in xs:
         hc.hc_fe_frombytes(x.to_bytes(32, "little"), h)
         y = x & (2**255 - 1)  # bit 255 (the sign bit) is ignored by the decoder
         assert val(h) % P == y % P and out_ok(h)
         hc.hc_fe_tobytes(h, out)
         assert int.from_bytes(out.raw, "little") == y % P
-    for _ in range(2000):  # tobytes of non-canonical reduced limb vectors
-        f = [r.randrange(-2**25, 2**25) if i % 2 == 0 else r.randrange(-2**24, 2**24) for i in range(10)]
+    for f in noncanon:  # tobytes of non-canonical reduced limb vectors
         hc.hc_fe_tobytes(arr(f), out)
         assert int.from_bytes(out.raw, "little") == val(f) % P
 
@@ -133,14 +103,13 @@ def test_fe_invert_safegcd():
     """The divsteps inversion the encode uses (V9) against pow(x, p - 2, p), on
     canonical, non-canonical and bound-extreme limb vectors."""
     hc = hostcheck_lib.load()
-    r = random.Random(17)
     h = (ctypes.c_int32 * 10)()
-    xs = [1, 2, 3, 19, P - 1, P - 2, (P - 1) // 2, 2**254, 2**255 - 20] + [r.randrange(1, P) for _ in range(3000)]
+    xs, vecs = fe_invert_cases()
+    assert len(xs) == 3009 and len(vecs) == 3000
     for x in xs:
         hc.hc_fe_invert_safegcd(arr(limbs(x)), h)
         assert val(h) % P == pow(x, P - 2, P) and out_ok(h), x
-    for it in range(3000):  # arbitrary (non-canonical, signed) limb vectors within the mul input bounds
-        f = rand_limbs(r, extreme=(it % 2 == 0))
+    for f in vecs:  # arbitrary (non-canonical, signed) limb vectors within the mul input bounds
         if val(f) % P == 0:
             continue
         hc.hc_fe_invert_safegcd(arr(f), h)
@@ -151,11 +120,9 @@ def test_fe_invert_safegcd():
 
 def test_sc_reduce_canonical():
     hc = hostcheck_lib.load()
-    r = random.Random(8)
     out = ctypes.create_string_buffer(32)
-    vals = [0, 1, L - 1, L, L + 1, 2 * L - 1, 2 * L, 2**512 - 1, 2**511, 2**253 - 1, 8 * L + 7]
-    vals += [k * L + d for k in (1, 2**100, 2**258 - 1) for d in (-1, 0, 1)]
-    vals += [r.randrange(2**512) for _ in range(3000)]
+    vals = sc_reduce_values()
+    assert len(vals) == 3020
     for v in vals:
         if not 0 <= v < 2**512:
             continue
@@ -198,28 +165,14 @@ def test_kernel_algorithm_on_cpu_matches_libsodium_golden(golden, golden_meta):
     assert bad == []
 
 
-def _digits(packed, bits):
-    """Digit k at bits [bits k, bits k + bits) of the packed 256-bit value."""
-    v = sum(w << (32 * i) for i, w in enumerate(packed))
-    out = []
-    for k in range(256 // bits):
-        raw = (v >> (bits * k)) & ((1 << bits) - 1)
-        out.append(raw - (1 << bits) if raw >> (bits - 1) else raw)
-    return out
-
-
 def test_scalar_recoding_radix_4_5_8():
     """Signed digits: radix 16 (the main loop's windows, digit in [-8, 7], so |d|
     indexes the 0..8 per-lane table) and radix 32, signer scalars (radix 256);
     sum d_k * 2^(bits*k) must give back the scalar."""
     hc = hostcheck_lib.load()
-    r = random.Random(12)
     out = (ctypes.c_uint32 * 8)()
-    # V2 admits every S < 2^252 and canonical S < L; h and signer scalars are < L
-    edge = [0, 1, L - 1, 2**252 - 1, 2**252, 2**253 - 1 - (2**253 - L)]
-    edge += [int("8000" * 16, 16) % L, int("7fff" * 16, 16) % L, int("ffff" * 15, 16), int("80" * 31, 16)]
-    edge += [int("88" * 31, 16), int("77" * 31, 16)]
-    vals = [v for v in edge if 0 <= v < L] + [r.randrange(L) for _ in range(2000)]
+    vals = recoding_values()
+    assert len(vals) >= 2010
     for bits, lo, hi in ((4, -8, 7), (5, -16, 15), (8, -128, 127)):
         for v in vals:
             assert hc.hc_recode(v.to_bytes(32, "little"), bits, out) == 0
@@ -277,37 +230,6 @@ def test_btab_entries_are_multiples_of_2_16t_B(bb):
             assert enc == orc.scalarmult_base(((j << (bb * t)) % L).to_bytes(32, "little")), (t, j)
 
 
-def _ed_add(p1, p2):
-    d = (-121665 * pow(121666, P - 2, P)) % P
-    (x1, y1), (x2, y2) = p1, p2
-    t = d * x1 * x2 * y1 * y2 % P
-    return ((x1 * y2 + y1 * x2) * pow(1 + t, P - 2, P) % P, (y1 * y2 + x1 * x2) * pow(1 - t, P - 2, P) % P)
-
-
-def _ed_decode(b):
-    d = (-121665 * pow(121666, P - 2, P)) % P
-    v = int.from_bytes(b, "little")
-    y, sign = v & ((1 << 255) - 1), v >> 255
-    if y >= P:
-        return None
-    u, w = (y * y - 1) % P, (d * y * y + 1) % P
-    x = pow(u * pow(w, P - 2, P), (P + 3) // 8, P)
-    if (w * x * x - u) % P:
-        x = x * pow(2, (P - 1) // 4, P) % P
-    if (w * x * x - u) % P:
-        return None
-    if x == 0 and sign:
-        return None
-    if (x & 1) != sign:
-        x = P - x
-    return x, y
-
-
-def _ed_encode(pt):
-    x, y = pt
-    return int.to_bytes(y | ((x & 1) << 255), 32, "little")
-
-
 @pytest.mark.parametrize("bb", sorted(SB_SHAPES))
 def test_r_side_point_is_SB_minus_R(bb):
     """The prep kernel's R side: Q = [S]B - R from the signed radix-2^bbits digits of S,
@@ -353,9 +275,6 @@ def test_r_side_point_is_SB_minus_R(bb):
         assert rside(Rb, (5).to_bytes(32, "little"), out) == -1, Rb.hex()
 
 
-N8L = 8 * L
-
-
 def _half(hc, h):
     a, u = ctypes.create_string_buffer(32), ctypes.create_string_buffer(32)
     neg = hc.hc_half_scalars(h.to_bytes(32, "little"), a, u)
@@ -368,21 +287,8 @@ def test_half_scalars_lattice_reduction():
     iff Q = 0 for Q in a group of order 8L), a >= 0, a < 2^253, |b| < 2^192 for
     every h < L, and both about 2^128 for hash-like h."""
     hc = hostcheck_lib.load()
-    r = random.Random(21)
-    edge = [0, 1, 2, 3, L - 1, L - 2, 2**128 - 1, 2**128, 2**128 + 1, 2**252, 2**252 - 1, 8, 2**64, 2**64 + 1]
-    # large partial quotients (the binary long-division path): h near N8L / 2^k and N8L * j / k
-    edge += [N8L >> k for k in (4, 40, 64, 100, 124, 130, 200) if (N8L >> k) < L]
-    edge += [(N8L >> k) + 1 for k in (40, 100, 126)]
-    edge += [(N8L * j // k) % L for j, k in ((1, 3), (2, 7), (5, 11), (1, 2**33 + 1), (7, 2**61 - 1))]
-    edge += [(2**140 * x) % L for x in (1, 3, 5)]
-    # a huge quotient after a few ordinary ones (negative cofactor at that point)
-    for k in (33, 40, 70, 110):
-        for q1 in (1, 2, 3):
-            x = N8L * 2**k // (q1 * 2**k + 1)          # N8L / h = q1 + 1/2^k
-            edge += [x % L, (x + 12345) % L]
-            x = N8L * (2**k + 1) // (2 * 2**k + 3)     # quotients 1, 1, ~2^(k-1), ...
-            edge += [x % L]
-    vals = edge + [r.randrange(L) for _ in range(20000)]
+    edge, vals = half_scalars_values()
+    assert len(vals) == len(edge) + 20000 and len(edge) >= 60
     lens = []
     for h in vals:
         a, b = _half(hc, h)
