@@ -6,8 +6,11 @@
  * profiling tools load libedv_measure.so beside the product library (a
  * second set of device contexts in the same process; device pointers from
  * either library are interchangeable) to time kernels on the kernels' own
- * stream, and the GPU tests use its fault hook.  Every edv.h entry point is
- * exported too, with the product's verdicts.
+ * stream, and the GPU tests use its fault hook, its math probes (the header
+ * functions on chosen inputs) and its stage probes (the prep kernel's state
+ * read back, the main kernel run on a chosen state, the device tables read
+ * back).  Every edv.h entry point is exported too, with the product's
+ * verdicts.
  */
 #ifndef EDV_MEASURE_H
 #define EDV_MEASURE_H
@@ -120,6 +123,69 @@ int edv_test_fail_async(int device, int64_t ticket);
 #define EDV_PROBE_QUAD_CACHED 19
 #define EDV_PROBE_QUAD_CACHED_SIGNED 20
 int edv_probe_math(int device, int op, const void *in, uint64_t in_stride, void *out, uint64_t out_stride, uint64_t n);
+
+/*
+ * Stage probes: the seam between the batch path's two launches.  The prep
+ * kernel hands the main kernel a per-chunk state in HBM (ChunkState,
+ * edv_kernels.h); these run the PRODUCT's kernels (the objects libedv.so is
+ * linked from; no probe adds device code) on a state the caller reads back or
+ * writes, so the GPU tests see every word prep stores and can walk states no
+ * SHA-512 output produces.  Host buffers in and out, device buffers that live
+ * for the call only, everything on the context's stream, one sync at the end.
+ * Bad arguments: EDV_E_ARG, edv_last_error() naming the probe.
+ *
+ * The state of n slots, as the kernels index it (cap = slot stride of the
+ * word-major arrays; 32-bit little-endian words):
+ *   array    words / bytes             contents
+ *   dig      17 x cap words            dig[w cap + j]: w 0..7 the 64 packed signed 4-bit digits of a,
+ *                                      8..15 of |b|, 16: window count | (b < 0) << 8
+ *   alive    3 x cap bytes             alive[k cap + j]: side k (0 hash, 1 A, 2 R) passed for slot j
+ *   atab     n x 360 words             atab[360 j + 40 e + 10 c + l]: limb l of coordinate c
+ *                                      (Y+X, Y-X, Z, 2dT) of entry e = 0..8, e x (-A)
+ *   rtab     n x 360 words             the same for e x ([S]B - R)
+ *   perm     n words                   slot j holds request perm[j] (length buckets; absent = identity)
+ *   accept   n bytes                   by REQUEST: 0 / 1 where a kernel wrote, else EDV_STAGE_SENTINEL
+ *
+ * edv_probe_prep_state: [bucket kernels,] prep kernel over n <= EDV_STAGE_CAP
+ * requests (sigs n x 64, pks n x 32, msgs, msg_off n + 1 absolute offsets into
+ * msgs) against table set `set` (EDV_TABLES_COMPACT / _LARGE, built if the GPU
+ * has not built it yet), sides side0 .. side0 + nsides - 1 in one launch, or
+ * with EDV_STAGE_SPLIT (side0 = 0, nsides = 3) as the split pipeline's two
+ * launches, 0 / 1 then 1 / 2.  EDV_STAGE_BUCKETS runs the length-bucket
+ * kernels first and returns perm.  Every state array and accept is filled
+ * with EDV_STAGE_SENTINEL bytes before the launches, so what comes back shows
+ * exactly which bytes the kernels wrote.  The arrays have cap = EDV_STAGE_CAP
+ * (reported in *cap); atab, rtab, perm and accept are copied for n slots.
+ *
+ * edv_probe_main_state: one launch of the main kernel (EDV_STAGE_PRIO: the
+ * split pipeline's edv_main_kernel_prio) on the caller's state of n <= cap <=
+ * EDV_STAGE_CAP slots; accept (n bytes, sentinel-filled first) comes back.
+ * perm may be null; its entries must be below n, and a live slot's window
+ * count at most 64 (the domain main_one documents).
+ *
+ * edv_probe_table: entries (t, j) = tj[2 k], tj[2 k + 1] of a device table as
+ * the context's kernels read it, 32 words each (y+x, y-x, 2dxy limbs, 2 words
+ * of padding): EDV_TABLES_COMPACT (16 x 32,769: j x 2^(16 t) B),
+ * EDV_TABLES_LARGE (12 x 2,097,153: j x 2^(22 t) B; builds the 3 GiB set if
+ * this GPU has none) or EDV_TABLES_COMB (the signer's 32 x 129: j x 256^t B).
+ * Device-side copies only, no kernel but a missing table's build.
+ */
+#define EDV_STAGE_CAP 4096
+#define EDV_STAGE_SENTINEL 0xA5
+#define EDV_STAGE_BUCKETS 1u
+#define EDV_STAGE_SPLIT 2u
+#define EDV_STAGE_PRIO 4u
+#define EDV_TABLES_COMPACT 0
+#define EDV_TABLES_LARGE 1
+#define EDV_TABLES_COMB 2
+int edv_probe_prep_state(int device, const uint8_t *sigs, const uint8_t *pks, const uint8_t *msgs,
+                         const uint64_t *msg_off, uint64_t n, int set, int side0, int nsides, uint32_t flags,
+                         uint32_t *dig, uint8_t *alive, int32_t *atab, int32_t *rtab, uint32_t *perm,
+                         uint8_t *accept, uint64_t *cap);
+int edv_probe_main_state(int device, uint64_t n, uint64_t cap, const uint32_t *dig, const uint8_t *alive,
+                         const int32_t *atab, const int32_t *rtab, const uint32_t *perm, uint32_t flags,
+                         uint8_t *accept);
+int edv_probe_table(int device, int set, const int32_t *tj, uint64_t n, int32_t *out);
 
 #ifdef __cplusplus
 }

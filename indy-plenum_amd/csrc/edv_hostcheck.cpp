@@ -215,6 +215,120 @@ int hc_probe_math(int op, const void* in, uint64_t in_stride, void* out, uint64_
   }
   return 0;
 }
+// The stage probes of include/edv_measure.h on the CPU build of the headers,
+// same state layout (dig[w cap + j], alive[k cap + j], atab / rtab 360 words
+// per slot, accept by request): the caller pre-fills every array with the
+// sentinel, these write what the kernels write.
+//
+// hc_stage_prep: prep_one, prep_point and prep_rpoint per slot, as
+// edv_prep_kernel's sides side0 .. side0 + nsides - 1 (a split run is the same
+// stores in another order).  buckets: perm = a stable counting sort by
+// sha_bucket (the device's order within a bucket is its atomics'), the
+// identity when every request shares one bucket.  bits: 16 or 22.
+static_assert(kAEntries * 40 == 360, "a slot's table is 9 entries of 4 x 10 limbs");
+int hc_stage_prep(const uint8_t* sigs, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, uint64_t n,
+                  int bits, int side0, int nsides, int buckets, uint64_t cap, uint32_t* dig, uint8_t* alive,
+                  int32_t* atab, int32_t* rtab, uint32_t* perm, uint8_t* accept) {
+  if ((bits != kBBits && bits != kBBitsCompact) || n > cap || side0 < 0 || nsides < 1 || side0 + nsides > 3) return -1;
+  const HostBTab& bt = btab(bits);
+  if (buckets) {
+    auto bucket = [&](uint64_t i) {
+      const uint64_t nb = (64 + (off[i + 1] - off[i]) + 17 + 127) / 128;
+      return nb < 63 ? nb : uint64_t(63);
+    };
+    uint64_t k = 0;
+    bool one = true;
+    for (uint64_t i = 1; i < n; i++) one = one && bucket(i) == bucket(0);
+    for (uint64_t b = 0; b < 64 && !one; b++)
+      for (uint64_t i = 0; i < n; i++)
+        if (bucket(i) == b) perm[k++] = uint32_t(i);
+    for (uint64_t i = 0; one && i < n; i++) perm[i] = uint32_t(i);
+  }
+  for (uint64_t j = 0; j < n; j++) {
+    const uint64_t i = buckets ? perm[j] : j;
+    uint32_t R[8], S[8], A[8];
+    load_words(R, sigs + 64 * i, 8);
+    load_words(S, sigs + 64 * i + 32, 8);
+    load_words(A, pks + 32 * i, 8);
+    for (int side = side0; side < side0 + nsides; side++) {
+      bool ok;
+      if (side == 0) {
+        const uint64_t mlen = off[i + 1] - off[i];
+        std::vector<uint8_t> buf(mlen + 32, 0);
+        if (mlen) memcpy(buf.data() + 16, msgs + off[i], mlen);
+        PrepDigits pd;
+        ok = prep_one(R, S, A, buf.data() + 16, mlen, pd);
+        if (ok) {
+          for (int k = 0; k < 8; k++) {
+            dig[uint64_t(k) * cap + j] = pd.da[k];
+            dig[uint64_t(8 + k) * cap + j] = pd.db[k];
+          }
+          dig[16 * cap + j] = uint32_t(pd.nwin) | (pd.negR ? 0x100u : 0u);
+        }
+      } else {
+        HostATab tab;
+        if (side == 1) {
+          ok = prep_point(A, tab);
+        } else {
+          HostBStage bs{bt};
+          ok = prep_rpoint(R, S, tab, bs);
+        }
+        int32_t* o = (side == 1 ? atab : rtab) + j * 360;
+        for (int e = 0; ok && e < kAEntries; e++) {
+          from_fe(o + 40 * e, tab.t[e].YpX);
+          from_fe(o + 40 * e + 10, tab.t[e].YmX);
+          from_fe(o + 40 * e + 20, tab.t[e].Z);
+          from_fe(o + 40 * e + 30, tab.t[e].T2d);
+        }
+      }
+      alive[uint64_t(side) * cap + j] = ok ? 1 : 0;
+      if (!ok) accept[i] = 0;
+    }
+  }
+  return 0;
+}
+// hc_stage_main: main_one on an injected state through a HostATab filled from
+// the buffers, as edv_main_kernel's body: a wave is 64 consecutive slots, its
+// window count the maximum over its live slots, dead slots untouched, slot
+// j's verdict at accept[perm ? perm[j] : j].
+int hc_stage_main(uint64_t n, uint64_t cap, const uint32_t* dig, const uint8_t* alive, const int32_t* atab,
+                  const int32_t* rtab, const uint32_t* perm, uint8_t* accept) {
+  if (n > cap) return -1;
+  auto live = [&](uint64_t j) { return j < n && alive[j] && alive[cap + j] && alive[2 * cap + j]; };
+  for (uint64_t w0 = 0; w0 < n; w0 += 64) {
+    int nwin = 0;
+    for (uint64_t j = w0; j < w0 + 64; j++)
+      if (live(j)) nwin = mx(nwin, int(dig[16 * cap + j] & 0xff));
+    if (nwin > kAWindows) return -1;
+    for (uint64_t j = w0; j < w0 + 64; j++) {
+      if (!live(j)) continue;
+      if (perm && perm[j] >= n) return -1;
+      uint32_t da[8], db[8];
+      for (int k = 0; k < 8; k++) {
+        da[k] = dig[uint64_t(k) * cap + j];
+        db[k] = dig[uint64_t(8 + k) * cap + j];
+      }
+      HostATab at, rt;
+      for (int e = 0; e < kAEntries; e++) {
+        const int32_t *a = atab + j * 360 + 40 * e, *r = rtab + j * 360 + 40 * e;
+        at.t[e] = ge_cached{to_fe(a), to_fe(a + 10), to_fe(a + 20), to_fe(a + 30)};
+        rt.t[e] = ge_cached{to_fe(r), to_fe(r + 10), to_fe(r + 20), to_fe(r + 30)};
+      }
+      accept[perm ? perm[j] : j] = main_one(da, db, nwin, (dig[16 * cap + j] >> 8) & 1, at, rt) ? 1 : 0;
+    }
+  }
+  return 0;
+}
+// entries (i, j) = ij[2 k], ij[2 k + 1] of the signer's comb (j x 256^i B), kBStride words each
+int hc_comb_entries(const int32_t* ij, int n, int32_t* out) {
+  const HostComb& ct = comb();
+  for (int k = 0; k < n; k++) {
+    if (ij[2 * k] < 0 || ij[2 * k] >= kCombRows || ij[2 * k + 1] < 0 || ij[2 * k + 1] >= kCombEntries) return -1;
+    memcpy(out + size_t(k) * kBStride, ct.w.data() + (ij[2 * k] * kCombEntries + ij[2 * k + 1]) * kBStride,
+           kBStride * sizeof(int32_t));
+  }
+  return 0;
+}
 // single-case forms of the ops the harness had no entry point for
 double hc_approx_div(double a, double b) { return approx_div(a, b); }
 double hc_fdiv_floor(double a, double b) { return fdiv_floor(a, b); }

@@ -25,7 +25,8 @@ hipError_t launch_sign_kernel(unsigned blocks, hipStream_t s, const uint32_t* se
                               const uint64_t* off, uint64_t msg_base, uint64_t n, uint32_t* pks, uint32_t* sigs,
                               const int32_t* comb);
 // the latency path (edv_quad.hip): requests base .. base + n - 1 of va in one
-// launch, four lanes per signature; qtab: n x kQSigWords words of scratch
+// launch, eight lanes per signature (sixteen in launch_rtl_kernel, below);
+// qtab: n x kQSigWords words of scratch
 hipError_t launch_quad_kernel(hipStream_t s, const VerifyArgs& va, int32_t* qtab);
 // the right-to-left latency kernel (no table scratch); at most kRtlMax requests
 hipError_t launch_rtl_kernel(hipStream_t s, const VerifyArgs& va);

@@ -1,7 +1,9 @@
 // edv_measure.inc -- the measurement entry points of libedv_measure.so
 // (include/edv_measure.h): kernel timing on the kernels' own stream, the
 // Infinity-Cache flush probe, the prep kernel's sides timed apart, the
-// asynchronous path's fault hook and the device math probes.  Included at the end of edv_runtime.hip only
+// asynchronous path's fault hook, the device math probes and the stage probes
+// (prep state out, main on a chosen state, table readback: host code around
+// the product's kernels, no device code).  Included at the end of edv_runtime.hip only
 // when EDV_MEASUREMENT_API is defined (the Makefile's libedv_measure.so); the
 // product libedv.so has none of it.
 #include "../../include/edv_measure.h"
@@ -32,6 +34,13 @@ __global__ __launch_bounds__(kBlock) void edv_flush_kernel(int4* p, uint64_t n16
     p[i] = v;
   }
 }
+
+// a device buffer of the stage probes: lives for the call only
+struct StageBuf : DevBuf {
+  ~StageBuf() {
+    if (p) (void)hipFree(p);
+  }
+};
 
 // elapsed ms between two events, accumulated
 int add_elapsed(float* acc, hipEvent_t a, hipEvent_t b) {
@@ -213,6 +222,175 @@ int edv_probe_math(int device, int op, const void* in, uint64_t in_stride, void*
         "probe launch");
   HIPOK(hipMemcpyAsync(out, dout.p, n * out_stride, hipMemcpyDeviceToHost, c->stream), "probe copy out");
   HIPOK(hipStreamSynchronize(c->stream), "probe sync");  // the buffers are freed on return
+  return 0;
+}
+
+// ---- the stage probes (include/edv_measure.h): the product's kernels on a
+// state the caller reads back or writes
+int edv_probe_prep_state(int device, const uint8_t* sigs, const uint8_t* pks, const uint8_t* msgs,
+                         const uint64_t* msg_off, uint64_t n, int set, int side0, int nsides, uint32_t flags,
+                         uint32_t* dig, uint8_t* alive, int32_t* atab, int32_t* rtab, uint32_t* perm, uint8_t* accept,
+                         uint64_t* cap_out) {
+  g_err.clear();
+  if (set != EDV_TABLES_COMPACT && set != EDV_TABLES_LARGE) return set_err(EDV_E_ARG, "prep probe: unknown table set");
+  if (side0 < 0 || nsides < 1 || side0 > 2 || nsides > 3 || side0 + nsides > 3)
+    return set_err(EDV_E_ARG, "prep probe: sides out of range");
+  if (flags & ~(EDV_STAGE_BUCKETS | EDV_STAGE_SPLIT)) return set_err(EDV_E_ARG, "prep probe: unknown flag");
+  if ((flags & EDV_STAGE_SPLIT) && !(side0 == 0 && nsides == 3))
+    return set_err(EDV_E_ARG, "prep probe: the split launches are sides 0 / 3");
+  if (n > EDV_STAGE_CAP) return set_err(EDV_E_ARG, "prep probe: at most EDV_STAGE_CAP requests");
+  const uint64_t cap = EDV_STAGE_CAP;
+  if (cap_out) *cap_out = cap;
+  if (n == 0) return 0;
+  const bool bucket = flags & EDV_STAGE_BUCKETS;
+  if (!sigs || !pks || !msg_off || !dig || !alive || !atab || !rtab || !accept || (bucket && !perm))
+    return set_err(EDV_E_ARG, "prep probe: null buffer");
+  for (uint64_t i = 0; i < n; i++)
+    if (msg_off[i + 1] < msg_off[i]) return set_err(EDV_E_ARG, "prep probe: msg_off not non-decreasing");
+  const uint64_t mbytes = msg_off[n];
+  if (mbytes && !msgs) return set_err(EDV_E_ARG, "prep probe: null buffer");
+  if (mbytes > (uint64_t(1) << 30)) return set_err(EDV_E_ARG, "prep probe: at most 1 GiB of messages");
+  CtxLock cl(device);
+  if (cl.err) return cl.err;
+  DevCtx* c = cl.c;
+  int err = 0;
+  const SbShape sh = set == EDV_TABLES_LARGE ? sb_large() : sb_compact();
+  const int32_t* tables = shared_tables(c->phys, sh, c->stream, &err);  // this GPU's set, built on first use
+  if (!tables) return err;
+  StageBuf dsigs, dpks, dmsgs, doff, dacc, datab, drtab, ddig, dalive, dperm, dctr;
+  if (dsigs.ensure(64 * n) || dpks.ensure(32 * n) || dmsgs.ensure(mbytes + 64) || doff.ensure(8 * (n + 1)) ||
+      dacc.ensure(n) || datab.ensure(n * kAWords * 4) || drtab.ensure(n * kAWords * 4) ||
+      ddig.ensure(cap * kDigWords * 4) || dalive.ensure(3 * cap) || dperm.ensure(4 * n) ||
+      dctr.ensure(2 * kBuckets * 4))
+    return EDV_E_OOM;
+  hipStream_t s = c->stream;
+  HIPOK(hipMemcpyAsync(dsigs.p, sigs, 64 * n, hipMemcpyHostToDevice, s), "prep probe copy in");
+  HIPOK(hipMemcpyAsync(dpks.p, pks, 32 * n, hipMemcpyHostToDevice, s), "prep probe copy in");
+  HIPOK(hipMemsetAsync(dmsgs.p, 0, mbytes + 64, s), "prep probe memset");  // the kernels read whole words past a message's end
+  if (mbytes) HIPOK(hipMemcpyAsync(dmsgs.p, msgs, mbytes, hipMemcpyHostToDevice, s), "prep probe copy in");
+  HIPOK(hipMemcpyAsync(doff.p, msg_off, 8 * (n + 1), hipMemcpyHostToDevice, s), "prep probe copy in");
+  HIPOK(hipMemsetAsync(dacc.p, EDV_STAGE_SENTINEL, n, s), "prep probe memset");
+  HIPOK(hipMemsetAsync(datab.p, EDV_STAGE_SENTINEL, n * kAWords * 4, s), "prep probe memset");
+  HIPOK(hipMemsetAsync(drtab.p, EDV_STAGE_SENTINEL, n * kAWords * 4, s), "prep probe memset");
+  HIPOK(hipMemsetAsync(ddig.p, EDV_STAGE_SENTINEL, cap * kDigWords * 4, s), "prep probe memset");
+  HIPOK(hipMemsetAsync(dalive.p, EDV_STAGE_SENTINEL, 3 * cap, s), "prep probe memset");
+  HIPOK(hipMemsetAsync(dperm.p, EDV_STAGE_SENTINEL, 4 * n, s), "prep probe memset");
+  VerifyArgs va;
+  va.sigs = static_cast<const uint32_t*>(dsigs.p);
+  va.pks = static_cast<const uint32_t*>(dpks.p);
+  va.msgs = static_cast<const uint8_t*>(dmsgs.p);
+  va.off = static_cast<const uint64_t*>(doff.p);
+  va.msg_base = 0;
+  va.base = 0;
+  va.n = n;
+  va.accept = static_cast<uint8_t*>(dacc.p);
+  va.st = ChunkState{static_cast<int32_t*>(datab.p), static_cast<int32_t*>(drtab.p), static_cast<uint32_t*>(ddig.p),
+                     static_cast<uint8_t*>(dalive.p), cap, bucket ? static_cast<uint32_t*>(dperm.p) : nullptr};
+  va.btab = tables;
+  va.sb = sh;
+  const unsigned blocks = unsigned((n + kBlock - 1) / kBlock);
+  if (bucket) {
+    HIPOK(hipMemsetAsync(dctr.p, 0, 2 * kBuckets * 4, s), "memset buckets");
+    HIPOK(launch_bucket_kernels(blocks, s, va.off, 0, n, static_cast<uint32_t*>(dctr.p),
+                                static_cast<uint32_t*>(dperm.p)),
+          "bucket launch");
+  }
+  const int32_t joint[1][2] = {{side0, nsides}}, split[2][2] = {{0, 1}, {1, 2}};  // (side0, nsides) per launch
+  const int32_t(*cfg)[2] = (flags & EDV_STAGE_SPLIT) ? split : joint;
+  for (int k = 0; k < ((flags & EDV_STAGE_SPLIT) ? 2 : 1); k++) {
+    va.side0 = cfg[k][0];
+    va.nsides = cfg[k][1];
+    HIPOK(launch_prep_kernel(unsigned(va.nsides) * blocks, s, va), "prep launch");
+  }
+  HIPOK(hipMemcpyAsync(dig, ddig.p, cap * kDigWords * 4, hipMemcpyDeviceToHost, s), "prep probe copy out");
+  HIPOK(hipMemcpyAsync(alive, dalive.p, 3 * cap, hipMemcpyDeviceToHost, s), "prep probe copy out");
+  HIPOK(hipMemcpyAsync(atab, datab.p, n * kAWords * 4, hipMemcpyDeviceToHost, s), "prep probe copy out");
+  HIPOK(hipMemcpyAsync(rtab, drtab.p, n * kAWords * 4, hipMemcpyDeviceToHost, s), "prep probe copy out");
+  if (bucket) HIPOK(hipMemcpyAsync(perm, dperm.p, 4 * n, hipMemcpyDeviceToHost, s), "prep probe copy out");
+  HIPOK(hipMemcpyAsync(accept, dacc.p, n, hipMemcpyDeviceToHost, s), "prep probe copy out");
+  HIPOK(hipStreamSynchronize(s), "prep probe sync");  // the buffers are freed on return
+  return 0;
+}
+
+int edv_probe_main_state(int device, uint64_t n, uint64_t cap, const uint32_t* dig, const uint8_t* alive,
+                         const int32_t* atab, const int32_t* rtab, const uint32_t* perm, uint32_t flags,
+                         uint8_t* accept) {
+  g_err.clear();
+  if (flags & ~EDV_STAGE_PRIO) return set_err(EDV_E_ARG, "main probe: unknown flag");
+  if (n > cap || cap > EDV_STAGE_CAP) return set_err(EDV_E_ARG, "main probe: n <= cap <= EDV_STAGE_CAP");
+  if (n == 0) return 0;
+  if (!dig || !alive || !atab || !rtab || !accept) return set_err(EDV_E_ARG, "main probe: null buffer");
+  // the domain the kernel is written for: verdicts land inside accept[0, n),
+  // a live slot walks at most kAWindows windows
+  for (uint64_t j = 0; j < n; j++) {
+    if (perm && perm[j] >= n) return set_err(EDV_E_ARG, "main probe: perm entry out of range");
+    if (alive[j] && alive[cap + j] && alive[2 * cap + j] && (dig[uint64_t(kDigNwin) * cap + j] & 0xff) > uint32_t(kAWindows))
+      return set_err(EDV_E_ARG, "main probe: window count above kAWindows");
+  }
+  CtxLock cl(device);
+  if (cl.err) return cl.err;
+  DevCtx* c = cl.c;
+  StageBuf dacc, datab, drtab, ddig, dalive, dperm;
+  if (dacc.ensure(n) || datab.ensure(n * kAWords * 4) || drtab.ensure(n * kAWords * 4) ||
+      ddig.ensure(cap * kDigWords * 4) || dalive.ensure(3 * cap) || (perm && dperm.ensure(4 * n)))
+    return EDV_E_OOM;
+  hipStream_t s = c->stream;
+  HIPOK(hipMemcpyAsync(ddig.p, dig, cap * kDigWords * 4, hipMemcpyHostToDevice, s), "main probe copy in");
+  HIPOK(hipMemcpyAsync(dalive.p, alive, 3 * cap, hipMemcpyHostToDevice, s), "main probe copy in");
+  HIPOK(hipMemcpyAsync(datab.p, atab, n * kAWords * 4, hipMemcpyHostToDevice, s), "main probe copy in");
+  HIPOK(hipMemcpyAsync(drtab.p, rtab, n * kAWords * 4, hipMemcpyHostToDevice, s), "main probe copy in");
+  if (perm) HIPOK(hipMemcpyAsync(dperm.p, perm, 4 * n, hipMemcpyHostToDevice, s), "main probe copy in");
+  HIPOK(hipMemsetAsync(dacc.p, EDV_STAGE_SENTINEL, n, s), "main probe memset");
+  VerifyArgs va{};
+  va.n = n;
+  va.accept = static_cast<uint8_t*>(dacc.p);
+  va.st = ChunkState{static_cast<int32_t*>(datab.p), static_cast<int32_t*>(drtab.p), static_cast<uint32_t*>(ddig.p),
+                     static_cast<uint8_t*>(dalive.p), cap, perm ? static_cast<uint32_t*>(dperm.p) : nullptr};
+  va.nsides = 3;
+  HIPOK(launch_main_kernel(unsigned((n + kBlock - 1) / kBlock), s, va, flags & EDV_STAGE_PRIO), "main launch");
+  HIPOK(hipMemcpyAsync(accept, dacc.p, n, hipMemcpyDeviceToHost, s), "main probe copy out");
+  HIPOK(hipStreamSynchronize(s), "main probe sync");  // the buffers are freed on return
+  return 0;
+}
+
+int edv_probe_table(int device, int set, const int32_t* tj, uint64_t n, int32_t* out) {
+  g_err.clear();
+  if (set != EDV_TABLES_COMPACT && set != EDV_TABLES_LARGE && set != EDV_TABLES_COMB)
+    return set_err(EDV_E_ARG, "table probe: unknown table set");
+  if (n > (uint64_t(1) << 20)) return set_err(EDV_E_ARG, "table probe: at most 2^20 entries");
+  if (n == 0) return 0;
+  if (!tj || !out) return set_err(EDV_E_ARG, "table probe: null buffer");
+  const SbShape sh = set == EDV_TABLES_LARGE ? sb_large() : sb_compact();
+  const int rows = set == EDV_TABLES_COMB ? kCombRows : sh.tables;
+  const int entries = set == EDV_TABLES_COMB ? kCombEntries : sh.entries;
+  for (uint64_t k = 0; k < n; k++)
+    if (tj[2 * k] < 0 || tj[2 * k] >= rows || tj[2 * k + 1] < 0 || tj[2 * k + 1] >= entries)
+      return set_err(EDV_E_ARG, "table probe: entry out of range");
+  CtxLock cl(device);
+  if (cl.err) return cl.err;
+  DevCtx* c = cl.c;
+  int err = 0;
+  const int32_t* table;
+  if (set == EDV_TABLES_COMB) {
+    if ((err = ensure_comb(*c))) return err;
+    table = c->comb;
+  } else if (!(table = shared_tables(c->phys, sh, c->stream, &err))) {
+    return err;
+  }
+  StageBuf stage;
+  if (stage.ensure(n * kBStride * 4)) return EDV_E_OOM;
+  // one device-side copy per run of consecutive entries, then one copy out
+  for (uint64_t k = 0; k < n;) {
+    uint64_t e = k + 1;
+    while (e < n && tj[2 * e] == tj[2 * k] && tj[2 * e + 1] == tj[2 * k + 1] + int32_t(e - k)) e++;
+    const int32_t* src = table + (size_t(tj[2 * k]) * size_t(entries) + size_t(tj[2 * k + 1])) * kBStride;
+    HIPOK(hipMemcpyAsync(static_cast<int32_t*>(stage.p) + k * kBStride, src, (e - k) * kBStride * 4,
+                         hipMemcpyDeviceToDevice, c->stream),
+          "table probe copy");
+    k = e;
+  }
+  HIPOK(hipMemcpyAsync(out, stage.p, n * kBStride * 4, hipMemcpyDeviceToHost, c->stream), "table probe copy out");
+  HIPOK(hipStreamSynchronize(c->stream), "table probe sync");  // the buffer is freed on return
   return 0;
 }
 

@@ -164,6 +164,10 @@ def measure_lib():
         h.edv_profile_prep_sides.argtypes = [vp, vp, vp, vp, u64, u64, vp, ctypes.c_int, ctypes.c_int, f32p]
         h.edv_test_fail_async.argtypes = [ctypes.c_int, ctypes.c_int64]
         h.edv_probe_math.argtypes = [ctypes.c_int, ctypes.c_int, vp, u64, vp, u64, u64]
+        h.edv_probe_prep_state.argtypes = [ctypes.c_int, vp, vp, vp, vp, u64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_uint32, vp, vp, vp, vp, vp, vp, ctypes.POINTER(u64)]
+        h.edv_probe_main_state.argtypes = [ctypes.c_int, u64, u64, vp, vp, vp, vp, vp, ctypes.c_uint32, vp]
+        h.edv_probe_table.argtypes = [ctypes.c_int, ctypes.c_int, vp, u64, vp]
         h.edv_verify_batch_async.argtypes = [vp, vp, vp, vp, u64, vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]
         h.edv_wait_async.argtypes = [ctypes.c_int, ctypes.c_int64]
         h.edv_last_error.restype = ctypes.c_char_p
@@ -242,8 +246,9 @@ LATENCY_PATH_DEFAULT = 16384
 
 
 def set_latency_path(device: int, max_requests: int):
-    """Batches of at most max_requests (0 = never) run on the four-lanes-per-
-    signature latency kernel (edv_set_latency_path).  Never changes verdicts."""
+    """Batches of at most max_requests (0 = never) run on the latency kernels:
+    sixteen lanes per signature up to 4,096 requests, eight above
+    (edv_set_latency_path).  Never changes verdicts."""
     _check(lib().edv_set_latency_path(device, max_requests))
 
 
@@ -645,4 +650,76 @@ def probe_math(op, cases, device=0):
     out = np.zeros((cases.shape[0], nout), np.uint8)
     _mcheck(measure_lib().edv_probe_math(device, code, cases.ctypes.data, nin, out.ctypes.data, nout,
                                          cases.shape[0]))
+    return out
+
+
+# ---- the stage probes (include/edv_measure.h): the product's prep and main
+# kernels on a state the caller reads back or writes, and the device tables
+STAGE_CAP = 4096
+STAGE_SENTINEL = 0xA5
+STAGE_BUCKETS, STAGE_SPLIT, STAGE_PRIO = 1, 2, 4
+TABLE_SETS = {"compact": 0, "large": 1, "comb": 2}
+A_WORDS = 360   # a slot's table: 9 entries x (Y+X, Y-X, Z, 2dT) x 10 limbs
+DIG_WORDS = 17
+
+
+def probe_prep_state(sigs, pks, msgs, offsets, table_set="compact", buckets=False, split=False, side0=0, nsides=3,
+                     device=0) -> dict:
+    """Runs the bucket kernels (if asked) and the prep kernel on a batch of at
+    most STAGE_CAP requests (edv_probe_prep_state) and returns the state they
+    wrote: dig (17, cap) uint32, alive (3, cap) uint8, atab / rtab (n, 360)
+    int32, perm (n) uint32 or None, accept (n) uint8; bytes no kernel wrote
+    hold STAGE_SENTINEL."""
+    sigs, pks, msgs = (np.ascontiguousarray(np.frombuffer(bytes(x), np.uint8) if isinstance(x, (bytes, bytearray))
+                                            else x, dtype=np.uint8) for x in (sigs, pks, msgs))
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = len(off) - 1
+    if sigs.size != 64 * n or pks.size != 32 * n or (n and msgs.size < int(off[-1])):
+        raise ValueError("prep probe: sigs n x 64, pks n x 32, msgs at least offsets[n] bytes")
+    cap = ctypes.c_uint64(0)
+    st = {"dig": np.full((DIG_WORDS, STAGE_CAP), STAGE_SENTINEL * 0x01010101, np.uint32),
+          "alive": np.full((3, STAGE_CAP), STAGE_SENTINEL, np.uint8),
+          "atab": np.full((n, A_WORDS), STAGE_SENTINEL * 0x01010101, np.uint32).view(np.int32),
+          "rtab": np.full((n, A_WORDS), STAGE_SENTINEL * 0x01010101, np.uint32).view(np.int32),
+          "perm": np.zeros(n, np.uint32) if buckets else None,
+          "accept": np.full(n, STAGE_SENTINEL, np.uint8)}
+    flags = (STAGE_BUCKETS if buckets else 0) | (STAGE_SPLIT if split else 0)
+    _mcheck(measure_lib().edv_probe_prep_state(
+        device, sigs.ctypes.data, pks.ctypes.data, msgs.ctypes.data, off.ctypes.data, n, TABLE_SETS[table_set], side0,
+        nsides, flags, st["dig"].ctypes.data, st["alive"].ctypes.data, st["atab"].ctypes.data, st["rtab"].ctypes.data,
+        st["perm"].ctypes.data if buckets else None, st["accept"].ctypes.data, ctypes.byref(cap)))
+    assert cap.value == STAGE_CAP
+    st["cap"] = STAGE_CAP
+    return st
+
+
+def probe_main_state(n, dig, alive, atab, rtab, perm=None, prio=False, device=0) -> np.ndarray:
+    """One launch of the main kernel (prio: edv_main_kernel_prio) on the given
+    state of n slots (edv_probe_main_state; dig (17, cap), alive (3, cap), atab
+    / rtab (n, 360)); returns accept (n) uint8, STAGE_SENTINEL where the kernel
+    wrote nothing."""
+    dig = np.ascontiguousarray(dig, dtype=np.uint32)
+    alive = np.ascontiguousarray(alive, dtype=np.uint8)
+    atab = np.ascontiguousarray(atab, dtype=np.int32)
+    rtab = np.ascontiguousarray(rtab, dtype=np.int32)
+    cap = dig.shape[1]
+    if dig.shape != (DIG_WORDS, cap) or alive.shape != (3, cap) or atab.size < n * A_WORDS or rtab.size < n * A_WORDS:
+        raise ValueError("main probe: dig (17, cap), alive (3, cap), atab / rtab n x 360 words")
+    if perm is not None:
+        perm = np.ascontiguousarray(perm, dtype=np.uint32)
+        if perm.size < n:
+            raise ValueError("main probe: perm has n entries")
+    accept = np.full(n, STAGE_SENTINEL, np.uint8)
+    _mcheck(measure_lib().edv_probe_main_state(device, n, cap, dig.ctypes.data, alive.ctypes.data, atab.ctypes.data,
+                                               rtab.ctypes.data, None if perm is None else perm.ctypes.data,
+                                               STAGE_PRIO if prio else 0, accept.ctypes.data))
+    return accept
+
+
+def probe_table(table_set, pairs, device=0) -> np.ndarray:
+    """Entries (t, j) of a device table (edv_probe_table: "compact", "large" or
+    "comb"), (n, 32) int32: y+x, y-x, 2dxy limbs and two words of padding."""
+    tj = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    out = np.zeros((len(tj), 32), np.int32)
+    _mcheck(measure_lib().edv_probe_table(device, TABLE_SETS[table_set], tj.ctypes.data, len(tj), out.ctypes.data))
     return out

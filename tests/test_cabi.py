@@ -32,7 +32,8 @@ def test_header_declares_the_core_entry_points():
         assert need in names
     meas = declared(MHDR)
     for need in ("edv_profile_batch_dev", "edv_profile_batch_dev_flush", "edv_time_batch_dev",
-                 "edv_profile_prep_sides", "edv_test_fail_async", "edv_probe_math"):
+                 "edv_profile_prep_sides", "edv_test_fail_async", "edv_probe_math", "edv_probe_prep_state",
+                 "edv_probe_main_state", "edv_probe_table"):
         assert need in meas and need not in names
 
 
@@ -54,7 +55,8 @@ def test_library_exports_every_declared_symbol():
     mblob = open(edv.MEASURE_LIB_PATH, "rb").read()
     assert b"edv_flush_kernel" not in blob and b"edv_flush_kernel" in mblob
     # the math probes (edv_probe_math) are the measurement build's alone
-    for name in (b"edv_probe_lane_kernel", b"edv_probe_quad_kernel", b"edv_probe_math"):
+    for name in (b"edv_probe_lane_kernel", b"edv_probe_quad_kernel", b"edv_probe_math", b"edv_probe_prep_state",
+                 b"edv_probe_main_state", b"edv_probe_table"):
         assert name not in blob and name in mblob
     noverify = os.path.join(os.path.dirname(edv.LIB_PATH), "variants", "libedv_noverify.so")
     if os.path.exists(noverify):
