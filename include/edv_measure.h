@@ -187,6 +187,51 @@ int edv_probe_main_state(int device, uint64_t n, uint64_t cap, const uint32_t *d
                          uint8_t *accept);
 int edv_probe_table(int device, int set, const int32_t *tj, uint64_t n, int32_t *out);
 
+/*
+ * Latency probes: the latency path's kernels (edv_quad.hip: edv_rtl_kernel,
+ * sixteen lanes per signature, and edv_quad_kernel, eight) cut at the barrier
+ * after their phase 1.  UNLIKE the stage probes above these are NOT the
+ * product's kernel objects: a latency kernel keeps its phase-1 results in LDS,
+ * so the probe kernels (edv_probe_latency.hip, this library only) instantiate
+ * the same header functions the product's kernels are made of
+ * (edv_quad_body.h: phase1, rtl_walk, quad_walk) around a copy of the LDS
+ * state to or from global memory.
+ *
+ * kernel: EDV_LAT_RTL (workgroups of 16 slots) or EDV_LAT_QUAD (32 slots).
+ * The state of G = ceil(n / slots per workgroup) workgroups of NS slots, every
+ * slot of every workgroup, padding slots included (32-bit words):
+ *   dig   G x 17 x NS words     dig[(g 17 + w) NS + j]: w 0..7 the packed signed 4-bit digits of a,
+ *                               8..15 of |b|, 16: window count | (b < 0) << 8
+ *   pt    G x 3 x 40 x NS words pt[((g 3 + k) 40 + w) NS + j]: point k (0: -A, 1: -R, 2: [S]B),
+ *                               extended coordinates X | Y | Z | T, 10 limbs each
+ *   ok    G x 3 x NS bytes      ok[(g 3 + k) NS + j]: side k (0 hash, 1 A, 2 R) passed
+ *
+ * edv_probe_latency_phase1: phase1<BITS, NS> over n <= EDV_STAGE_CAP requests
+ * against table set `set` (EDV_TABLES_COMPACT / _LARGE), exactly as the
+ * product kernel runs it; after the barrier each workgroup copies its L.dig,
+ * L.pt and L.ok out.  dig, pt, ok and accept (n bytes: phase 1 writes no
+ * verdict) are filled with EDV_STAGE_SENTINEL bytes first.
+ *
+ * edv_probe_latency_walk: the caller gives the phase-1 state of all `slots`
+ * slots (n rounded up to the workgroup's 16 or 32); each workgroup fills its
+ * LDS from it, executes the barrier and runs rtl_walk / quad_walk unchanged
+ * (the two-walk variant on table scratch sized as the product sizes it).
+ * accept (`slots` bytes, sentinel-filled first: the kernels write verdicts
+ * for slots below n only) comes back.  flags: none defined, must be 0.  A slot with its three ok bytes set must have a window count of
+ * at most 64, the domain the walks (and the right-to-left kernel's counter
+ * protocol) are written for.
+ *
+ * Both: n = 0 returns EDV_OK with nothing launched; bad arguments return
+ * EDV_E_ARG, edv_last_error() naming the probe.
+ */
+#define EDV_LAT_RTL 0
+#define EDV_LAT_QUAD 1
+int edv_probe_latency_phase1(int device, int kernel, int set, const uint8_t *sigs, const uint8_t *pks,
+                             const uint8_t *msgs, const uint64_t *msg_off, uint64_t n, uint32_t *dig, int32_t *pt,
+                             uint8_t *ok, uint8_t *accept);
+int edv_probe_latency_walk(int device, int kernel, uint64_t n, uint64_t slots, const uint32_t *dig, const int32_t *pt,
+                           const uint8_t *ok, uint32_t flags, uint8_t *accept);
+
 #ifdef __cplusplus
 }
 #endif

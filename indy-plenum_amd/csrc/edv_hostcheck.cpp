@@ -319,6 +319,119 @@ int hc_stage_main(uint64_t n, uint64_t cap, const uint32_t* dig, const uint8_t* 
   }
   return 0;
 }
+// The latency probes of include/edv_measure.h on the CPU.  The latency
+// kernels' quad code (edv_quad_body.h) has no CPU build, so these are
+// REFERENCES, not the code under test: they prove the cases and the Python
+// checkers here before the same families run on the device.  State layout
+// [word][slot] with stride slots = n rounded up to ns (16 or 32):
+// dig[w slots + j], pt[(k 40 + w) slots + j], ok[k slots + j].
+//
+// hc_stage_latency_phase1: what phase1<BITS, NS> leaves in LDS, from the
+// one-lane header functions (prep_one; ge_is_canonical / has_small_order /
+// ge_frombytes_negate; add_sb from the identity), with the kernels' padding
+// rule: slots n .. 15 repeat the last request, later ones are not worked.
+namespace {
+void put_p3(int32_t* pt, int k, uint64_t slots, uint64_t j, const ge_p3& p) {
+  const fe* c[4] = {&p.X, &p.Y, &p.Z, &p.T};
+  for (int q = 0; q < 4; q++)
+    for (int i = 0; i < 10; i++) pt[(uint64_t(k) * 40 + 10 * q + i) * slots + j] = c[q]->v[i];
+}
+ge_p3 get_p3(const int32_t* pt, int k, uint64_t slots, uint64_t j) {
+  fe c[4];
+  for (int q = 0; q < 4; q++)
+    for (int i = 0; i < 10; i++) c[q].v[i] = pt[(uint64_t(k) * 40 + 10 * q + i) * slots + j];
+  return ge_p3{c[0], c[1], c[2], c[3]};
+}
+ge_p3 p3_add(const ge_p3& p, const ge_p3& q) { return ge_p1p1_to_p3(ge_add(p, ge_p3_to_cached(q))); }
+ge_p3 p3_neg(const ge_p3& p) { return ge_p3{fe_neg(p.X), p.Y, p.Z, fe_neg(p.T)}; }
+// sum_k d_k 16^k P over the 64 signed 4-bit digits packed in d, most
+// significant first: four doublings, then + d_k P
+ge_p3 signed_digit_mult(const uint32_t d[8], bool negate, const ge_p3& P) {
+  ge_p3 m[9];
+  m[0] = ge_p3_identity();
+  for (int e = 1; e < 9; e++) m[e] = p3_add(m[e - 1], P);
+  ge_p3 acc = ge_p3_identity();
+  for (int k = 63; k >= 0; k--) {
+    for (int t = 0; t < 4; t++) acc = ge_p1p1_to_p3(ge_p2_dbl(ge_p3_to_p2(acc)));
+    int dg = int(d[k / 8] >> (4 * (k % 8))) & 15;
+    if (dg >= 8) dg -= 16;
+    if (negate) dg = -dg;
+    if (dg) acc = p3_add(acc, dg < 0 ? p3_neg(m[-dg]) : m[dg]);
+  }
+  return acc;
+}
+}  // namespace
+int hc_stage_latency_phase1(const uint8_t* sigs, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off,
+                            uint64_t n, int ns, int bits, uint32_t* dig, int32_t* pt, uint8_t* ok) {
+  if ((bits != kBBits && bits != kBBitsCompact) || (ns != 16 && ns != 32) || n == 0) return -1;
+  const HostBTab& bt = btab(bits);
+  const uint64_t slots = (n + ns - 1) / ns * ns;
+  for (uint64_t jl = 0; jl < slots; jl++) {
+    const bool in = jl < n || jl < 16;
+    const uint64_t i = jl < n ? jl : n - 1;
+    bool ok0 = false, ok1 = false, ok2 = false;
+    PrepDigits pd;
+    ge_p3 pa = ge_p3_identity(), pr = ge_p3_identity(), sb = ge_p3_identity();
+    if (in) {
+      uint32_t R[8], S[8], A[8];
+      load_words(R, sigs + 64 * i, 8);
+      load_words(S, sigs + 64 * i + 32, 8);
+      load_words(A, pks + 32 * i, 8);
+      const uint64_t mlen = off[i + 1] - off[i];
+      std::vector<uint8_t> buf(mlen + 32, 0);
+      if (mlen) memcpy(buf.data() + 16, msgs + off[i], mlen);
+      ok0 = prep_one(R, S, A, buf.data() + 16, mlen, pd);
+      ok1 = ge_is_canonical(A) && !has_small_order(A) && ge_frombytes_negate(pa, A);
+      if (!ok1) pa = ge_p3_identity();
+      ok2 = ge_is_canonical(R) && !has_small_order(R) && ge_frombytes_negate(pr, R);
+      if (!ok2) pr = ge_p3_identity();
+      HostBStage bs{bt};
+      add_sb(sb, S, bs);
+    }
+    for (int k = 0; k < 8; k++) {
+      dig[uint64_t(k) * slots + jl] = ok0 ? pd.da[k] : 0u;
+      dig[uint64_t(8 + k) * slots + jl] = ok0 ? pd.db[k] : 0u;
+    }
+    dig[16 * slots + jl] = ok0 ? (uint32_t(pd.nwin) | (pd.negR ? 0x100u : 0u)) : 0u;
+    ok[jl] = ok0;
+    ok[slots + jl] = ok1;
+    ok[2 * slots + jl] = ok2;
+    put_p3(pt, 0, slots, jl, pa);
+    put_p3(pt, 1, slots, jl, pr);
+    put_p3(pt, 2, slots, jl, sb);
+  }
+  return 0;
+}
+// hc_stage_latency_walk: the verdict of every slot below n from the injected
+// state, [a]P1 + [+-b]([S]B + (-R)) == identity by plain signed-digit
+// double-and-add with ge_* of edv_math.h over all 64 digits (a slot's digits
+// past its window count are zero in the domain the probe accepts), with the
+// kernels' alive / in / padding rules: a slot some side killed gets 0, slots
+// n .. write nothing.
+int hc_stage_latency_walk(uint64_t n, int ns, const uint32_t* dig, const int32_t* pt, const uint8_t* ok,
+                          uint8_t* accept) {
+  if ((ns != 16 && ns != 32) || n == 0) return -1;
+  const uint64_t slots = (n + ns - 1) / ns * ns;
+  for (uint64_t j = 0; j < n; j++) {
+    const bool alive = ok[j] && ok[slots + j] && ok[2 * slots + j];
+    if (!alive) {
+      accept[j] = 0;
+      continue;
+    }
+    const uint32_t wf = dig[16 * slots + j];
+    if ((wf & 0xff) > uint32_t(kAWindows)) return -1;
+    uint32_t da[8], db[8];
+    for (int k = 0; k < 8; k++) {
+      da[k] = dig[uint64_t(k) * slots + j];
+      db[k] = dig[uint64_t(8 + k) * slots + j];
+    }
+    const ge_p3 q = p3_add(get_p3(pt, 2, slots, j), get_p3(pt, 1, slots, j));
+    const ge_p3 r = p3_add(signed_digit_mult(da, false, get_p3(pt, 0, slots, j)),
+                           signed_digit_mult(db, (wf >> 8) & 1, q));
+    accept[j] = (fe_iszero(r.X) && fe_iszero(fe_sub(r.Y, r.Z))) ? 1 : 0;
+  }
+  return 0;
+}
 // entries (i, j) = ij[2 k], ij[2 k + 1] of the signer's comb (j x 256^i B), kBStride words each
 int hc_comb_entries(const int32_t* ij, int n, int32_t* out) {
   const HostComb& ct = comb();

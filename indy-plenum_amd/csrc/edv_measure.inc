@@ -3,7 +3,9 @@
 // Infinity-Cache flush probe, the prep kernel's sides timed apart, the
 // asynchronous path's fault hook, the device math probes and the stage probes
 // (prep state out, main on a chosen state, table readback: host code around
-// the product's kernels, no device code).  Included at the end of edv_runtime.hip only
+// the product's kernels, no device code) and the latency probes (phase 1 out,
+// walk on a chosen state: probe kernels of edv_probe_latency.hip, which
+// instantiate edv_quad.hip's header functions).  Included at the end of edv_runtime.hip only
 // when EDV_MEASUREMENT_API is defined (the Makefile's libedv_measure.so); the
 // product libedv.so has none of it.
 #include "../../include/edv_measure.h"
@@ -391,6 +393,115 @@ int edv_probe_table(int device, int set, const int32_t* tj, uint64_t n, int32_t*
   }
   HIPOK(hipMemcpyAsync(out, stage.p, n * kBStride * 4, hipMemcpyDeviceToHost, c->stream), "table probe copy out");
   HIPOK(hipStreamSynchronize(c->stream), "table probe sync");  // the buffer is freed on return
+  return 0;
+}
+
+// ---- the latency probes (include/edv_measure.h): probe kernels that
+// instantiate edv_quad.hip's phase 1 and walks (edv_probe_latency.hip), NOT
+// the product's kernel objects
+int edv_probe_latency_phase1(int device, int kernel, int set, const uint8_t* sigs, const uint8_t* pks,
+                             const uint8_t* msgs, const uint64_t* msg_off, uint64_t n, uint32_t* dig, int32_t* pt,
+                             uint8_t* ok, uint8_t* accept) {
+  g_err.clear();
+  const uint64_t ns = uint64_t(probe_latency_sigs(kernel));
+  if (!ns) return set_err(EDV_E_ARG, "latency phase-1 probe: unknown kernel");
+  if (set != EDV_TABLES_COMPACT && set != EDV_TABLES_LARGE)
+    return set_err(EDV_E_ARG, "latency phase-1 probe: unknown table set");
+  if (n > EDV_STAGE_CAP) return set_err(EDV_E_ARG, "latency phase-1 probe: at most EDV_STAGE_CAP requests");
+  if (n == 0) return 0;
+  if (!sigs || !pks || !msg_off || !dig || !pt || !ok || !accept)
+    return set_err(EDV_E_ARG, "latency phase-1 probe: null buffer");
+  for (uint64_t i = 0; i < n; i++)
+    if (msg_off[i + 1] < msg_off[i]) return set_err(EDV_E_ARG, "latency phase-1 probe: msg_off not non-decreasing");
+  const uint64_t mbytes = msg_off[n];
+  if (mbytes && !msgs) return set_err(EDV_E_ARG, "latency phase-1 probe: null buffer");
+  if (mbytes > (uint64_t(1) << 30)) return set_err(EDV_E_ARG, "latency phase-1 probe: at most 1 GiB of messages");
+  CtxLock cl(device);
+  if (cl.err) return cl.err;
+  DevCtx* c = cl.c;
+  int err = 0;
+  const SbShape sh = set == EDV_TABLES_LARGE ? sb_large() : sb_compact();
+  const int32_t* tables = shared_tables(c->phys, sh, c->stream, &err);  // this GPU's set, built on first use
+  if (!tables) return err;
+  const uint64_t slots = (n + ns - 1) / ns * ns;
+  const uint64_t dig_b = slots * 17 * 4, pt_b = slots * 3 * 40 * 4, ok_b = slots * 3;
+  StageBuf dsigs, dpks, dmsgs, doff, dacc, ddig, dpt, dok;
+  if (dsigs.ensure(64 * n) || dpks.ensure(32 * n) || dmsgs.ensure(mbytes + 64) || doff.ensure(8 * (n + 1)) ||
+      dacc.ensure(n) || ddig.ensure(dig_b) || dpt.ensure(pt_b) || dok.ensure(ok_b))
+    return EDV_E_OOM;
+  hipStream_t s = c->stream;
+  HIPOK(hipMemcpyAsync(dsigs.p, sigs, 64 * n, hipMemcpyHostToDevice, s), "latency probe copy in");
+  HIPOK(hipMemcpyAsync(dpks.p, pks, 32 * n, hipMemcpyHostToDevice, s), "latency probe copy in");
+  HIPOK(hipMemsetAsync(dmsgs.p, 0, mbytes + 64, s), "latency probe memset");  // whole words are read past a message's end
+  if (mbytes) HIPOK(hipMemcpyAsync(dmsgs.p, msgs, mbytes, hipMemcpyHostToDevice, s), "latency probe copy in");
+  HIPOK(hipMemcpyAsync(doff.p, msg_off, 8 * (n + 1), hipMemcpyHostToDevice, s), "latency probe copy in");
+  HIPOK(hipMemsetAsync(dacc.p, EDV_STAGE_SENTINEL, n, s), "latency probe memset");
+  HIPOK(hipMemsetAsync(ddig.p, EDV_STAGE_SENTINEL, dig_b, s), "latency probe memset");
+  HIPOK(hipMemsetAsync(dpt.p, EDV_STAGE_SENTINEL, pt_b, s), "latency probe memset");
+  HIPOK(hipMemsetAsync(dok.p, EDV_STAGE_SENTINEL, ok_b, s), "latency probe memset");
+  VerifyArgs va;
+  memset(&va, 0, sizeof va);
+  va.sigs = static_cast<const uint32_t*>(dsigs.p);
+  va.pks = static_cast<const uint32_t*>(dpks.p);
+  va.msgs = static_cast<const uint8_t*>(dmsgs.p);
+  va.off = static_cast<const uint64_t*>(doff.p);
+  va.n = n;
+  va.accept = static_cast<uint8_t*>(dacc.p);
+  va.btab = tables;
+  va.sb = sh;
+  HIPOK(launch_probe_latency_phase1(s, kernel, va, static_cast<uint32_t*>(ddig.p), static_cast<int32_t*>(dpt.p),
+                                    static_cast<uint8_t*>(dok.p)),
+        "latency phase-1 probe launch");
+  HIPOK(hipMemcpyAsync(dig, ddig.p, dig_b, hipMemcpyDeviceToHost, s), "latency probe copy out");
+  HIPOK(hipMemcpyAsync(pt, dpt.p, pt_b, hipMemcpyDeviceToHost, s), "latency probe copy out");
+  HIPOK(hipMemcpyAsync(ok, dok.p, ok_b, hipMemcpyDeviceToHost, s), "latency probe copy out");
+  HIPOK(hipMemcpyAsync(accept, dacc.p, n, hipMemcpyDeviceToHost, s), "latency probe copy out");
+  HIPOK(hipStreamSynchronize(s), "latency probe sync");  // the buffers are freed on return
+  return 0;
+}
+
+int edv_probe_latency_walk(int device, int kernel, uint64_t n, uint64_t slots, const uint32_t* dig, const int32_t* pt,
+                           const uint8_t* ok, uint32_t flags, uint8_t* accept) {
+  g_err.clear();
+  const uint64_t ns = uint64_t(probe_latency_sigs(kernel));
+  if (!ns) return set_err(EDV_E_ARG, "latency walk probe: unknown kernel");
+  if (flags) return set_err(EDV_E_ARG, "latency walk probe: unknown flag");
+  if (n > EDV_STAGE_CAP) return set_err(EDV_E_ARG, "latency walk probe: at most EDV_STAGE_CAP requests");
+  if (n == 0) return 0;
+  if (slots != (n + ns - 1) / ns * ns)
+    return set_err(EDV_E_ARG, "latency walk probe: slots is n rounded up to the workgroup's 16 or 32");
+  if (!dig || !pt || !ok || !accept) return set_err(EDV_E_ARG, "latency walk probe: null buffer");
+  // the domain the walks are written for: a slot all three sides passed walks
+  // at most kAWindows windows (the right-to-left kernel's waves meet through
+  // counters that run to the window count: never driven outside it)
+  for (uint64_t g = 0; g < slots / ns; g++)
+    for (uint64_t j = 0; j < ns; j++)
+      if (ok[(g * 3 + 0) * ns + j] && ok[(g * 3 + 1) * ns + j] && ok[(g * 3 + 2) * ns + j] &&
+          (dig[(g * 17 + 16) * ns + j] & 0xff) > uint32_t(kAWindows))
+        return set_err(EDV_E_ARG, "latency walk probe: window count above kAWindows");
+  CtxLock cl(device);
+  if (cl.err) return cl.err;
+  DevCtx* c = cl.c;
+  const uint64_t dig_b = slots * 17 * 4, pt_b = slots * 3 * 40 * 4, ok_b = slots * 3;
+  StageBuf dacc, ddig, dpt, dok, dqtab;
+  if (dacc.ensure(slots) || ddig.ensure(dig_b) || dpt.ensure(pt_b) || dok.ensure(ok_b)) return EDV_E_OOM;
+  // the two-walk kernel's table scratch, as launch_quad sizes it (the last
+  // workgroup's 64 quads all write their tables, in range or not)
+  if (kernel == EDV_LAT_QUAD && dqtab.ensure((n + 63) / 64 * 64 * kQSigWords * 4)) return EDV_E_OOM;
+  hipStream_t s = c->stream;
+  HIPOK(hipMemcpyAsync(ddig.p, dig, dig_b, hipMemcpyHostToDevice, s), "latency probe copy in");
+  HIPOK(hipMemcpyAsync(dpt.p, pt, pt_b, hipMemcpyHostToDevice, s), "latency probe copy in");
+  HIPOK(hipMemcpyAsync(dok.p, ok, ok_b, hipMemcpyHostToDevice, s), "latency probe copy in");
+  HIPOK(hipMemsetAsync(dacc.p, EDV_STAGE_SENTINEL, slots, s), "latency probe memset");
+  VerifyArgs va;
+  memset(&va, 0, sizeof va);
+  va.n = n;
+  va.accept = static_cast<uint8_t*>(dacc.p);
+  HIPOK(launch_probe_latency_walk(s, kernel, va, static_cast<int32_t*>(dqtab.p), static_cast<const uint32_t*>(ddig.p),
+                                  static_cast<const int32_t*>(dpt.p), static_cast<const uint8_t*>(dok.p)),
+        "latency walk probe launch");
+  HIPOK(hipMemcpyAsync(accept, dacc.p, slots, hipMemcpyDeviceToHost, s), "latency probe copy out");
+  HIPOK(hipStreamSynchronize(s), "latency probe sync");  // the buffers are freed on return
   return 0;
 }
 

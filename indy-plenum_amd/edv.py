@@ -168,6 +168,9 @@ def measure_lib():
                                            ctypes.c_uint32, vp, vp, vp, vp, vp, vp, ctypes.POINTER(u64)]
         h.edv_probe_main_state.argtypes = [ctypes.c_int, u64, u64, vp, vp, vp, vp, vp, ctypes.c_uint32, vp]
         h.edv_probe_table.argtypes = [ctypes.c_int, ctypes.c_int, vp, u64, vp]
+        h.edv_probe_latency_phase1.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, u64, vp, vp,
+                                               vp, vp]
+        h.edv_probe_latency_walk.argtypes = [ctypes.c_int, ctypes.c_int, u64, u64, vp, vp, vp, ctypes.c_uint32, vp]
         h.edv_verify_batch_async.argtypes = [vp, vp, vp, vp, u64, vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]
         h.edv_wait_async.argtypes = [ctypes.c_int, ctypes.c_int64]
         h.edv_last_error.restype = ctypes.c_char_p
@@ -723,3 +726,68 @@ def probe_table(table_set, pairs, device=0) -> np.ndarray:
     out = np.zeros((len(tj), 32), np.int32)
     _mcheck(measure_lib().edv_probe_table(device, TABLE_SETS[table_set], tj.ctypes.data, len(tj), out.ctypes.data))
     return out
+
+
+# ---- the latency probes (include/edv_measure.h): the latency kernels cut at
+# phase 1's barrier.  Probe kernels that instantiate the header functions the
+# product's kernels are made of, not the product's kernel objects.
+LAT_KERNELS = {"rtl": (0, 16), "quad": (1, 32)}   # name -> (code, slots per workgroup)
+PT_WORDS = 40    # a point: X | Y | Z | T, 10 limbs each
+
+
+def latency_slots(kernel, n) -> int:
+    """n rounded up to the workgroup's 16 or 32 slots"""
+    ns = LAT_KERNELS[kernel][1]
+    return (n + ns - 1) // ns * ns
+
+
+def probe_latency_phase1(kernel, sigs, pks, msgs, offsets, table_set="compact", device=0) -> dict:
+    """Phase 1 of a latency kernel ("rtl" or "quad") over at most STAGE_CAP
+    requests (edv_probe_latency_phase1); returns what each workgroup held in
+    LDS at the barrier, by slot: dig (17, slots) uint32, pt (3, 40, slots)
+    int32, ok (3, slots) uint8, and accept (n) uint8; bytes no kernel wrote
+    hold STAGE_SENTINEL."""
+    code, ns = LAT_KERNELS[kernel]
+    sigs, pks, msgs = (np.ascontiguousarray(np.frombuffer(bytes(x), np.uint8) if isinstance(x, (bytes, bytearray))
+                                            else x, dtype=np.uint8) for x in (sigs, pks, msgs))
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = len(off) - 1
+    if sigs.size != 64 * n or pks.size != 32 * n or (n and msgs.size < int(off[-1])):
+        raise ValueError("latency phase-1 probe: sigs n x 64, pks n x 32, msgs at least offsets[n] bytes")
+    slots = latency_slots(kernel, n)
+    g = slots // ns
+    dig = np.full((g, DIG_WORDS, ns), STAGE_SENTINEL * 0x01010101, np.uint32)
+    pt = np.full((g, 3, PT_WORDS, ns), STAGE_SENTINEL * 0x01010101, np.uint32).view(np.int32)
+    ok = np.full((g, 3, ns), STAGE_SENTINEL, np.uint8)
+    accept = np.full(n, STAGE_SENTINEL, np.uint8)
+    _mcheck(measure_lib().edv_probe_latency_phase1(
+        device, code, TABLE_SETS[table_set], sigs.ctypes.data, pks.ctypes.data, msgs.ctypes.data, off.ctypes.data, n,
+        dig.ctypes.data, pt.ctypes.data, ok.ctypes.data, accept.ctypes.data))
+    # [workgroup][word][slot] -> [word][slot of the batch]
+    return {"dig": np.ascontiguousarray(dig.transpose(1, 0, 2).reshape(DIG_WORDS, slots)),
+            "pt": np.ascontiguousarray(pt.transpose(1, 2, 0, 3).reshape(3, PT_WORDS, slots)),
+            "ok": np.ascontiguousarray(ok.transpose(1, 0, 2).reshape(3, slots)), "accept": accept, "slots": slots}
+
+
+def probe_latency_walk(kernel, n, dig, pt, ok, device=0) -> np.ndarray:
+    """Everything after phase 1's barrier of a latency kernel ("rtl" or "quad")
+    on the given phase-1 state (edv_probe_latency_walk): dig (17, slots), pt
+    (3, 40, slots), ok (3, slots) with slots = latency_slots(kernel, n);
+    returns accept (slots) uint8, STAGE_SENTINEL where the kernel wrote nothing
+    (every slot from n on)."""
+    code, ns = LAT_KERNELS[kernel]
+    slots = latency_slots(kernel, n)
+    dig = np.asarray(dig, dtype=np.uint32)
+    pt = np.asarray(pt, dtype=np.int32)
+    ok = np.asarray(ok, dtype=np.uint8)
+    if dig.shape != (DIG_WORDS, slots) or pt.shape != (3, PT_WORDS, slots) or ok.shape != (3, slots):
+        raise ValueError("latency walk probe: dig (17, slots), pt (3, 40, slots), ok (3, slots)")
+    g = slots // ns
+    # [word][slot of the batch] -> [workgroup][word][slot]
+    dig = np.ascontiguousarray(dig.reshape(DIG_WORDS, g, ns).transpose(1, 0, 2))
+    pt = np.ascontiguousarray(pt.reshape(3, PT_WORDS, g, ns).transpose(2, 0, 1, 3))
+    ok = np.ascontiguousarray(ok.reshape(3, g, ns).transpose(1, 0, 2))
+    accept = np.full(slots, STAGE_SENTINEL, np.uint8)
+    _mcheck(measure_lib().edv_probe_latency_walk(device, code, n, slots, dig.ctypes.data, pt.ctypes.data,
+                                                 ok.ctypes.data, 0, accept.ctypes.data))
+    return accept

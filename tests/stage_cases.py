@@ -4,7 +4,9 @@ kernels: the per-chunk state edv_prep_kernel writes and edv_main_kernel reads
 like math_cases.py: `host` is the CPU build of the headers behind the same
 state layout (libedv_hostcheck.so: hc_stage_prep, hc_stage_main,
 hc_btab_entries_of_bits, hc_comb_entries), `device` is the product's kernels
-run by the stage probes of libedv_measure.so (include/edv_measure.h).
+run by the stage probes of libedv_measure.so (include/edv_measure.h).  The
+last section does the same for the latency kernels cut at phase 1's barrier
+(the latency probes; there `host` is a reference, see that section).
 
 A checker takes its expected values from hashlib, Python integers, the affine
 Edwards arithmetic of math_cases and the oracle's scalarmult_base only, never
@@ -790,3 +792,520 @@ def family_round_trip(backend, table_set="compact", buckets=True, split=False, p
     got = round_trip(backend, b, PREP_N, prep_state(backend, PREP_N, table_set, buckets, split), prio)
     assert got == [int(q["valid"]) for q in b["reqs"]]
     return got
+
+
+# ====================================================== the latency kernels
+# edv_quad.hip's kernels cut at the barrier after their phase 1 (the latency
+# probes of include/edv_measure.h): what phase 1 leaves in LDS read back, and
+# the walks (rtl_walk, quad_walk) run on chosen phase-1 states.  `device` is the
+# probe kernels of libedv_measure.so, which instantiate the product kernels'
+# own header functions; `host` is a CPU reference (hc_stage_latency_phase1 /
+# _walk: the one-lane header functions and plain signed-digit double-and-add),
+# there to prove the cases and checkers, not a build of the code under test.
+#
+# A phase-1 state of `slots` slots (n rounded up to the workgroup's 16 or 32):
+# dig (17, slots), pt (3, 40, slots): -A, -R, [S]B in extended coordinates
+# (X | Y | Z | T, 10 limbs each), ok (3, slots).  Limb bound: every coordinate
+# phase 1 stores is a product (ge_frombytes_negate's X, Y and T = X Y, with Z =
+# 1; add_sb's result through ge_p1p1_to_p3) or the negation of one, and
+# edv_math.h states fe_mul's output bound as RED; the quad formulas are proved
+# for operands inside RED (math_cases.family_quad_points / quad_bounds).
+LAT_NS = {"rtl": 16, "quad": 32}      # slots per workgroup
+LAT_UNIT = {"rtl": 16, "quad": 8}     # slots that share a window count: the workgroup, or a wave's 8 signatures
+LAT_MIN_LIVE = 16                     # kQMinLive
+LAT_P1_SIZES = (1, 15, 16, 17, 33, PREP_N)
+LAT_WALK_SIZES = (1, 3, 15, 16, 17, 31, 32, 33)
+
+
+def lat_slots(kernel, n):
+    ns = LAT_NS[kernel]
+    return (n + ns - 1) // ns * ns
+
+
+def _hc_lat():
+    hc = hostcheck_lib.load()
+    vp, u64, ci = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int
+    hc.hc_stage_latency_phase1.argtypes = [vp, vp, vp, vp, u64, ci, ci, vp, vp, vp]
+    hc.hc_stage_latency_walk.argtypes = [u64, ci, vp, vp, vp, vp]
+    return hc
+
+
+def run_lat_phase1(backend, kernel, batch, n, table_set="compact"):
+    """phase 1 over the first n requests of `batch` -> dig, pt, ok by slot, accept (n), slots"""
+    sigs, pks, off = batch["sigs"][:64 * n], batch["pks"][:32 * n], batch["off"][:n + 1]
+    msgs = batch["msgs"]
+    if backend == "device":
+        from indy_plenum_amd import edv
+        return edv.probe_latency_phase1(kernel, sigs, pks, msgs, off, table_set)
+    assert backend == "host"
+    slots = lat_slots(kernel, n)
+    st = {"dig": np.full((17, slots), SENT32, np.uint32), "pt": np.full((3, 40, slots), SENT32, np.uint32).view(np.int32),
+          "ok": np.full((3, slots), SENT, np.uint8), "accept": np.full(n, SENT, np.uint8), "slots": slots}
+    sigs, pks, off = np.ascontiguousarray(sigs), np.ascontiguousarray(pks), np.ascontiguousarray(off)
+    assert _hc_lat().hc_stage_latency_phase1(sigs.ctypes.data, pks.ctypes.data, msgs.ctypes.data, off.ctypes.data, n,
+                                             LAT_NS[kernel], SET_BITS[table_set], st["dig"].ctypes.data,
+                                             st["pt"].ctypes.data, st["ok"].ctypes.data) == 0
+    return st
+
+
+def run_lat_walk(backend, kernel, n, dig, pt, ok):
+    """the walk on a phase-1 state -> accept (slots) uint8, SENT where nothing was written"""
+    if backend == "device":
+        from indy_plenum_amd import edv
+        return edv.probe_latency_walk(kernel, n, dig, pt, ok)
+    assert backend == "host"
+    slots = lat_slots(kernel, n)
+    dig, pt = np.ascontiguousarray(dig, np.uint32), np.ascontiguousarray(pt, np.int32)
+    ok = np.ascontiguousarray(ok, np.uint8)
+    assert dig.shape == (17, slots) and pt.shape == (3, 40, slots) and ok.shape == (3, slots)
+    accept = np.full(slots, SENT, np.uint8)
+    assert _hc_lat().hc_stage_latency_walk(n, LAT_NS[kernel], dig.ctypes.data, pt.ctypes.data, ok.ctypes.data,
+                                           accept.ctypes.data) == 0
+    return accept
+
+
+# ------------------------------------------------------------- walk in: cases
+def push_to_red(l):
+    """the same value with every limb that can cross to the opposite sign inside
+    RED moved there (one limb width, carried into the next limb): limbs at the
+    outer edge of what phase 1 can emit"""
+    l = list(l)
+    for i in range(9):
+        w = 26 if i % 2 == 0 else 25
+        edge = (1 << (w - 1)) - (1 << 20) + 2
+        if abs(l[i]) >= edge:
+            s = 1 if l[i] > 0 else -1
+            l[i] -= s << w
+            l[i + 1] += s
+    return l
+
+
+def ext_limbs(r, pt, mode):
+    """the 40 words X | Y | Z | T (T = X Y / Z) of the affine point: Z = 1
+    ("affine"), a random Z ("scaled"), or Z's limbs at +-RED and the other
+    coordinates' limbs pushed outwards where they can be ("bound"); every limb
+    inside RED, the bound of what phase 1 stores"""
+    x, y = pt
+    if mode == "bound":
+        zl = mc.red_limbs(r, extreme=True)
+        z = mc.val(zl) % P
+        assert z
+    else:
+        z = 1 if mode == "affine" else r.randrange(1, P)
+        zl = mc.signed_limbs(z)
+    want = [x * z % P, y * z % P, z, x * y * z % P]
+    coords = [mc.signed_limbs(v) for v in want]
+    if mode == "bound":
+        coords = [push_to_red(c) for c in coords]
+    coords[2] = zl
+    assert all(abs(v) <= RED[i] for c in coords for i, v in enumerate(c)), "a limb outside what phase 1 can emit"
+    assert [mc.val(c) % P for c in coords] == want
+    return [v for c in coords for v in c]
+
+
+def _digits_value(digits):
+    return sum(d << (4 * k) for k, d in enumerate(digits))
+
+
+def one_bucket_scalars():
+    """(bucket, digit sign, scalar): scalars whose signed digits all have the
+    magnitude `bucket` (a run of negative digits needs one positive digit on top:
+    the same magnitude, or for -8 the 1 of 0x77..78); bucket 0 is the scalar 0"""
+    out = [(0, 1, 0)]
+    for d in range(1, 9):
+        if d < 8:
+            out.append((d, 1, _digits_value([d] * 40)))
+            out.append((d, -1, _digits_value([-d] * 40 + [d])))
+        else:
+            out.append((8, -1, int("7" * 62 + "8", 16)))            # 63 digits of -8, then 1
+            out.append((8, -1, int("7" * 20 + "8", 16)))
+    for d, sign, s in out:
+        dg = recode4(s)[0]
+        body = dg[:windows(dg) - (1 if sign < 0 else 0)]           # below the positive digit on top of a negative run
+        assert all(x == sign * d for x in body) and len(body) >= 21 * bool(s), (d, sign, hex(s))
+        assert {abs(x) for x in dg[:windows(dg)]} <= ({d} if d < 8 else {8, 1}), (d, sign, hex(s))
+    return out
+
+
+EVERY_BUCKET = _digits_value([1, -2, 3, -4, 5, -6, 7, -8, 0, 8 - 16, 6, -5, 4, -3, 2, -1, 0, 1])
+
+
+def _twin_case(r, a, u, negR):
+    """[b]P2 = [a]P1 + T with T = (0, -1), the point of order 2: b m = a k (mod L) and b j - a i = 4 (mod 8)"""
+    sb = -u if negR else u
+    k = r.randrange(1, L)
+    m = a * k * pow(sb, L - 2, L) % L
+    i = r.randrange(8)
+    j = next(j for j in range(8) if (sb * j - a * i) % 8 == 4)
+    own = own_count(a, u)
+    c = {"a": a, "u": u, "neg": negR, "k": k, "m": m, "i": i, "j": j, "word": own, "mode": "affine", "alive": (1, 1, 1),
+         "tag": "x twin", "own": own}
+    c["expect"] = expected_verdict(c)
+    assert c["expect"] == 0
+    return c
+
+
+class _Tally:
+    """requested and dropped cases per family (a case whose congruences have no solution is dropped)"""
+    def __init__(self):
+        self.asked, self.dropped = {}, {}
+
+    def __call__(self, family, cases):
+        self.asked[family] = self.asked.get(family, 0) + len(cases)
+        self.dropped[family] = self.dropped.get(family, 0) + sum(1 for c in cases if c is None)
+        out = [c for c in cases if c is not None]
+        for c in out:
+            c["family"] = family
+        return out
+
+
+@functools.lru_cache(maxsize=None)
+def lat_cases(kernel):
+    """-> (slots, tally): the slots of the chosen phase-1 state of one latency
+    kernel, grouped by the unit that shares a window count (16: the right-to-left
+    kernel's workgroup, 8: a wave's signatures in the two-walk kernel); the last
+    workgroup is partial"""
+    U, ns = LAT_UNIT[kernel], LAT_NS[kernel]
+    r = random.Random(1717 + U)
+    short = lambda: r.randrange(1, 2**12) | 1                                   # noqa: E731
+    tally, units = _Tally(), []
+
+    def add(family, cases, fill=U):
+        cases = tally(family, cases)
+        for o in range(0, len(cases), fill):
+            w = cases[o:o + fill]
+            units.append(w + [_dead(r) for _ in range(U - len(w))])
+
+    # every window count 1..64 for a and for |b|, accepted and off by one; half a unit of cases, half dead
+    for which in "ab":
+        cs = []
+        for c in range(1, 65):
+            s = _scalar_with_count(r, c)
+            tiny = r.randrange(1, 8) if c <= 3 else short() + (c & 1)
+            a, u = (s, tiny) if which == "a" else (tiny, s)
+            cs += [_case(r, a, u, c & 1, tag="count %s %d" % (which, c)),
+                   _case(r, a, u, c & 1, k_off=1, tag="count %s %d off by one" % (which, c))]
+        add("count " + which, cs, fill=U // 2)
+    # one long walk among short ones, at the first and the last slot of the unit
+    for pos in (0, U - 1):
+        w = [_case(r, short(), short(), k & 1, k_off=(k % 5 == 4), tag="spike short") for k in range(U)]
+        w[pos] = _case(r, _scalar_with_count(r, 64), short(), 0, tag="spike 64")
+        w[(pos + 3) % U] = _case(r, short(), _scalar_with_count(r, 33), 1, tag="spike 33")
+        w[(pos + 5) % U] = _case(r, short(), short(), 1, alive=(1, 1, 0), tag="spike dead")
+        add("spike", w)
+    # the count word above the slot's own count
+    cs = []
+    for it in range(32):
+        a, u = _scalar_with_count(r, 1 + it % 20), short()
+        own = own_count(a, u)
+        cs.append(_case(r, a, u, it & 1, word=(own + 1, max(own, 33), 64)[it % 3], k_off=(it % 4 == 3),
+                        tag="count word above own"))
+    add("word above own", cs)
+    # digit families on a and on |b|, accepted and off by one
+    cs = []
+    for s in special_scalars():
+        cs += [_case(r, s, short(), 0, tag="digits a")]
+        if s:
+            cs += [_case(r, s, short(), 1, k_off=1, tag="digits a off by one"),
+                   _case(r, short() * 2, s, 1, tag="digits b"), _case(r, short(), s, 0, k_off=1, tag="digits b off by one")]
+    add("special scalars", cs)
+    cs = []
+    for c in (3, 4, 17, 33, 34, 48, 49, 63, 64):
+        s = _scalar_with_count(r, c, carry_top=True)
+        cs += [_case(r, s, short(), 0, tag="carry top a"), _case(r, short(), s, 1, tag="carry top b"),
+               _case(r, s, short(), 1, k_off=1, tag="carry top a off by one")]
+    add("carry top", cs)
+    add("a = 0", [_case(r, 0, u, s, tag="a = 0") for u in (1, 3, 2**100 + 1, 2**191 + 1) for s in (0, 1)])
+    # both signs of the same |b|, solved for one of them
+    cs = []
+    for it in range(16):
+        a, u = r.getrandbits(130), r.getrandbits(128) | 1
+        c0 = _case(r, a, u, it & 1, tag="sign")
+        c1 = dict(c0, neg=1 - c0["neg"], tag="sign flipped")
+        c1["expect"] = expected_verdict(c1)
+        assert c0["expect"] == 1 and c1["expect"] == 0
+        cs += [c0, c1]
+    add("sign", cs)
+    # results of order 2 (X = 0, Y = -Z), 4 and 8
+    cs = []
+    for it in range(48):
+        a, u = r.getrandbits(128) | (it & 1), r.getrandbits(127) | 1
+        res = (4, 2, 6, 1, 3, 7, 5, 4)[it % 8]
+        cs.append(_case(r, a, u, it & 1, residue=res, tag="small-order result %d" % res))
+    add("small-order result", cs)
+    # [b]P2 = [a]P1 + (0, -1): the two results have X_a = -X_b as an accepted pair has, and Y_a = -Y_b;
+    # only the final check's Y condition rejects it
+    add("x twin", [_twin_case(r, r.getrandbits(120 + it) | 1, r.getrandbits(100 + it) | 1, it & 1) for it in range(8)])
+    # each ok byte cleared in turn on states that would be accepted, the digits left in place
+    cs = []
+    for it in range(2 * U):
+        al = ((1, 1, 1), (0, 1, 1), (1, 0, 1), (1, 1, 0))[it % 4]
+        cs.append(_case(r, r.getrandbits(126), r.getrandbits(126) | 1, it & 1, alive=al, tag="ok %s" % (al,)))
+    add("ok cleared", cs)
+    if kernel == "rtl":
+        # workgroup maxima: the ring's wrap, the running-sum phase from every nwin % kRing
+        for top in (0, 1, 2, 3, 4, 5, 7, 8, 9, 63, 64):
+            if top == 0:
+                units.append([dict(_dead(r), family="maximum 0") for _ in range(U)])
+                tally("maximum 0", units[-1])
+                continue
+            cs = []
+            for k in range(U - 2):
+                c = top if k % 4 == 0 else r.randrange(1, top + 1)
+                a, u = _scalar_with_count(r, c), (r.randrange(1, 8) if top < 4 else _scalar_with_count(r, min(c, 3))) | 1
+                if k % 2:
+                    a, u = (u, a | 1) if own_count(u, a | 1) <= top else (a, u)
+                cs.append(_case(r, a, u, k & 1, k_off=(k % 3 == 2), tag="maximum %d" % top))
+            assert max(c["word"] for c in cs) == top, top
+            add("maximum %d" % top, cs)
+        # all digits in one bucket, each bucket and digit sign, on a and on |b|, both signs of b
+        cs = []
+        for d, sign, s in one_bucket_scalars():
+            cs += [_case(r, s, short(), 0, tag="bucket %d a" % d), _case(r, s, 1, 1, k_off=(s != 0), tag="bucket %d a x" % d)]
+            if s & 1:
+                cs += [_case(r, short(), s, ng, k_off=ng, tag="bucket %d b" % d) for ng in (0, 1)]
+                cs += [_case(r, 1, s, ng, tag="bucket %d b 1" % d) for ng in (0, 1)]
+        cs += [_case(r, EVERY_BUCKET, short(), 0, tag="every bucket a"), _case(r, short(), EVERY_BUCKET, 1, tag="every bucket b"),
+               _case(r, EVERY_BUCKET, EVERY_BUCKET, 0, k_off=1, tag="every bucket off by one")]
+        add("buckets", cs, fill=U // 2)
+    else:
+        # the four waves of one workgroup with maxima 1, 16, 33 and 64 at once
+        while len(units) % (ns // U):
+            units.append([_dead(r) for _ in range(U)])
+        for top in (1, 16, 33, 64):
+            cs = [_case(r, r.randrange(1, 8), r.randrange(1, 8) | 1, k & 1, k_off=k & 1, tag="waves %d" % top) if top == 1 else
+                  _case(r, _scalar_with_count(r, top if k == 3 else r.randrange(1, top + 1)), short(), k & 1,
+                        k_off=(k % 3 == 0), tag="waves %d" % top) for k in range(U)]
+            assert max(c["word"] for c in cs) == top
+            add("waves", cs)
+    # a partial last workgroup
+    while len(units) % (ns // U):
+        units.append([_dead(r) for _ in range(U)])
+    tail = tally("tail", [_case(r, r.getrandbits(128), r.getrandbits(128) | 1, it & 1, k_off=(it % 3 == 0), tag="tail")
+                          for it in range(5)])
+    slots = [c for w in units for c in w] + tail
+    # the cap on dropped cases: a condition on the builder, not a measurement
+    asked, dropped = sum(tally.asked.values()), sum(tally.dropped.values())
+    assert dropped * 50 <= asked, (dropped, asked)
+    assert tally.dropped["count a"] == 0 and tally.dropped["count b"] == 0
+    want = {"count a", "count b", "spike", "word above own", "special scalars", "carry top", "a = 0", "sign",
+            "small-order result", "x twin", "ok cleared", "tail"}
+    want |= ({"buckets"} | {"maximum %d" % t for t in (0, 1, 2, 3, 4, 5, 7, 8, 9, 63, 64)}) if kernel == "rtl" else {"waves"}
+    have = {c.get("family") for c in slots}
+    assert want <= have, want - have
+    return slots, tally
+
+
+def _x_point(r, torsion):
+    pt = base_mult(r.randrange(1, L))
+    return mc.ed_add(pt, TORSION[r.randrange(1, 8)]) if torsion else pt
+
+
+def lat_state_of(cases, kernel, seed=919):
+    """the phase-1 state of the slots `cases`, padded to whole workgroups with
+    live-looking accepted states: pt[0] = P1, pt[2] = X = [s]B (half the slots
+    with a torsion component), pt[1] = P2 - X, so the kernel's own [S]B + (-R) is
+    P2; the three point forms in turn.  A dead slot: garbage digits, count 64,
+    arbitrary limbs inside the bound."""
+    r = random.Random(seed)
+    cases = list(cases)
+    while len(cases) % LAT_NS[kernel]:
+        cases.append(_case(r, r.getrandbits(100), r.getrandbits(100) | 1, len(cases) & 1, tag="past the batch"))
+    slots = len(cases)
+    dig, ok = np.zeros((17, slots), np.uint32), np.zeros((3, slots), np.uint8)
+    pt = np.zeros((3, 40, slots), np.int32)
+    for s, c in enumerate(cases):
+        ok[:, s] = c["alive"]
+        if c.get("dead"):
+            dig[:, s] = c["words"]
+            pt[:, :, s] = [[v for _ in range(4) for v in mc.red_limbs(r)] for _ in range(3)]
+            continue
+        dig[0:8, s] = recode4(c["a"])[1]
+        dig[8:16, s] = recode4(c["u"])[1]
+        dig[16, s] = c["word"] | (c["neg"] << 8)
+        p1 = mc.ed_add(base_mult(c["k"]), TORSION[c["i"]]) if c["k"] % L else TORSION[c["i"]]
+        p2 = mc.ed_add(base_mult(c["m"]), TORSION[c["j"]]) if c["m"] % L else TORSION[c["j"]]
+        x = _x_point(r, s & 1)
+        c["p1"], c["p2"], c["x"], c["mr"] = p1, p2, x, mc.ed_add(p2, neg(x))
+        mode = ("affine", "scaled", "bound")[s % 3]
+        pt[0, :, s], pt[1, :, s], pt[2, :, s] = ext_limbs(r, p1, mode), ext_limbs(r, c["mr"], mode), ext_limbs(r, x, mode)
+    return cases, dig, pt, ok
+
+
+@functools.lru_cache(maxsize=None)
+def lat_state(kernel):
+    slots, _ = lat_cases(kernel)
+    return (len(slots),) + lat_state_of(slots, kernel)
+
+
+def lat_expected(cases, n, slots):
+    """accept after the walk: 0 for a slot below n with an ok byte cleared, its verdict otherwise; SENT from n on"""
+    return [(c["expect"] if all(c["alive"]) else 0) if s < n else SENT for s, c in enumerate(cases[:slots])]
+
+
+def check_lat_accept(kernel, cases, n, got):
+    slots = lat_slots(kernel, n)
+    got, want = [int(v) for v in got], lat_expected(cases, n, slots)
+    assert len(got) == slots
+    bad = [(s, cases[s]["tag"], got[s], want[s]) for s in range(slots) if got[s] != want[s]]
+    assert bad == [], (kernel, n, bad[:12])
+
+
+def check_lat_walk(backend, kernel):
+    """the whole chosen state of the kernel through its walk, every accept byte checked"""
+    n, cases, dig, pt, ok = lat_state(kernel)
+    check_lat_accept(kernel, cases, n, run_lat_walk(backend, kernel, n, dig, pt, ok))
+    return n
+
+
+@functools.lru_cache(maxsize=None)
+def _lat_plain(kernel):
+    """64 plain slots for the batch sizes: accepted, rejected, one ok byte cleared"""
+    r = random.Random(2323)
+    cs = []
+    for it in range(64):
+        al = (1, 1, 1) if it % 7 != 5 else ((0, 1, 1), (1, 0, 1), (1, 1, 0))[it % 3]
+        cs.append(_case(r, r.getrandbits(40 + 3 * it), r.getrandbits(30 + 2 * it) | 1, it & 1, k_off=(it % 3 == 1), alive=al,
+                        tag="plain"))
+    return cs
+
+
+def check_lat_sizes(backend, kernel, n):
+    """A batch of n slots in whole workgroups.  Below kQMinLive the padding slots
+    n .. 15 are worked: they carry a live state with count 64 that would be
+    accepted, and in a second run one that would be rejected; neither may change
+    a verdict below n, and nothing is written from n on."""
+    r = random.Random(31 * n)
+    slots = lat_slots(kernel, n)
+    base = _lat_plain(kernel)[:slots]
+    runs = []
+    for k_off in ((0, 1) if n < LAT_MIN_LIVE else (0,)):
+        cs = list(base)
+        for s in range(n, min(slots, LAT_MIN_LIVE)):
+            cs[s] = _case(r, _scalar_with_count(r, 64), r.getrandbits(60) | 1, s & 1, k_off=k_off, tag="padding %d" % k_off)
+        cases, dig, pt, ok = lat_state_of(cs, kernel, seed=n)
+        got = run_lat_walk(backend, kernel, n, dig, pt, ok)
+        check_lat_accept(kernel, cases, n, got)
+        runs.append(got.tolist())
+    assert all(g == runs[0] for g in runs)
+
+
+def check_lat_construction(kernel, count=120):
+    """The construction itself: for a spread of the slots, the injected -R and
+    [S]B add up to P2 and [a]P1 + [b]P2 by plain double-and-add is the identity
+    exactly when the case expects an accept; the small-order cases land on a
+    point of the order they name.  Read back from the limbs that are injected."""
+    n, cases, dig, pt, ok = lat_state(kernel)
+    live = [s for s, c in enumerate(cases) if not c.get("dead")]
+    picked = live[::max(1, len(live) // count)] + [s for s in live if cases[s]["tag"].startswith("small-order")][:16]
+    picked += [s for s in live if cases[s]["tag"] == "x twin"]
+    seen = set()
+    for s in picked:
+        c = cases[s]
+        p1, mr, x = (mc.affine([[int(v) for v in pt[k, 10 * q:10 * q + 10, s]] for q in range(4)]) for k in range(3))
+        assert p1 == c["p1"] and mc.ed_add(x, mr) == c["p2"] and x == c["x"], (s, c["tag"], "the X / P2 - X split")
+        sb = -c["u"] if c["neg"] else c["u"]
+        q = ext_add(double_and_add(c["a"], p1), double_and_add(sb, mc.ed_add(x, mr)))
+        xy = affine_all([q])[0]
+        assert (xy == IDENT) == bool(c["expect"]), c["tag"]
+        if c["tag"] == "x twin":                     # what the X condition alone accepts
+            pa, pb = affine_all([double_and_add(c["a"], p1), double_and_add(sb, c["p2"])])
+            assert (pa[0] + pb[0]) % P == 0 and (pa[1] + pb[1]) % P == 0 and pa[1] != pb[1] and pa[0], c["tag"]
+            seen.add("twin")
+        if c["tag"].startswith("small-order"):
+            order = next(o for o in (1, 2, 4, 8) if affine_all([double_and_add(o, xy)])[0] == IDENT)
+            res = int(c["tag"].split()[-1])
+            assert order == {4: 2, 2: 4, 6: 4}.get(res, 8), (c["tag"], order)
+            seen.add(order)
+    assert seen == {2, 4, 8, "twin"}
+    return len(picked)
+
+
+# ------------------------------------------------------------ phase 1 out
+def _is_identity(words40):
+    x, y, z, t = _vals(words40)
+    return x == 0 and t == 0 and y == z != 0
+
+
+def check_lat_phase1(kernel, batch, n, st, sb_enc=None):
+    """Every word phase 1 left for the first n requests against Python and the
+    oracle; -> the (a, b) pairs by request (None where the hash side rejected)"""
+    reqs, slots = batch["reqs"], lat_slots(kernel, n)
+    assert st["slots"] == slots and st["dig"].shape == (17, slots) and st["pt"].shape == (3, 40, slots)
+    assert st["ok"].shape == (3, slots)
+    assert (st["accept"] == SENT).all(), "phase 1 writes no verdict"
+    assert not (st["dig"] == SENT32).any() and not (st["pt"].view(np.uint32) == SENT32).any(), "a word left sentinel"
+    assert (st["ok"] <= 1).all(), "an ok byte left sentinel"
+    assert (np.abs(st["pt"].astype(np.int64)) <= np.array(RED * 4)[None, :, None]).all(), "a limb outside RED"
+    if sb_enc is None:
+        sb_enc = oracle_base_mults([q["S"] % 2**253 for q in reqs[:n]])
+    ab = [None] * n
+    for s in range(slots):
+        worked = s < n or s < LAT_MIN_LIVE
+        w = [int(v) for v in st["dig"][:, s]]
+        pts = [[int(v) for v in st["pt"][k, :, s]] for k in range(3)]
+        oks = tuple(int(st["ok"][k, s]) for k in range(3))
+        if not worked:
+            assert oks == (0, 0, 0) and not any(w) and all(_is_identity(p) for p in pts), (s, "a slot past the batch")
+            continue
+        if s >= n:                                    # padding repeats the last request, word for word
+            for key in ("dig", "pt", "ok"):
+                assert (st[key][..., s] == st[key][..., n - 1]).all(), (s, key, "padding")
+            continue
+        q = reqs[s]
+        assert oks == q["sides"], (s, q["kind"], oks, "ok")
+        if oks[0]:
+            a, b, da, db, cnt = unpack_dig(st, s)
+            assert 0 <= a < 2**253 and abs(b) < 2**192 and b % 2 == 1, (s, "scalar range")
+            assert (a - b * q["h"]) % N8L == 0, (s, "a = b h mod 8L")
+            assert da[63] >= 0 and db[63] >= 0 and all(-8 <= d <= 7 for d in da + db), (s, "digit range")
+            assert cnt == max(windows(da), windows(db)), (s, "window count", cnt)
+            ab[s] = (a, b)
+        else:
+            assert not any(w), (s, "digits of a rejected request")
+        for k, enc in ((0, q["A"]), (1, q["R"])):
+            if oks[k + 1]:
+                x, y = neg(point_of(enc))
+                X, Y, Z, T = _vals(pts[k])
+                assert Z and X == x * Z % P and Y == y * Z % P and T * Z % P == X * Y % P, (s, k, "point")
+            else:
+                assert _is_identity(pts[k]), (s, k, "a rejected point")
+        X, Y, Z, T = _vals(pts[2])                     # [S]B whatever the sides say (S cut to 253 bits)
+        assert Z and T * Z % P == X * Y % P, (s, "[S]B T")
+        zi = pow(Z, P - 2, P)
+        x, y = X * zi % P, Y * zi % P
+        assert int.to_bytes(y | ((x & 1) << 255), 32, "little") == sb_enc[s], (s, "[S]B")
+    return ab
+
+
+@functools.lru_cache(maxsize=None)
+def lat_phase1_state(backend, kernel, n, table_set):
+    return run_lat_phase1(backend, kernel, prep_batch(), n, table_set)
+
+
+@functools.lru_cache(maxsize=None)
+def _sb_encodings():
+    return oracle_base_mults([q["S"] % 2**253 for q in prep_batch()["reqs"]])
+
+
+def family_lat_phase1(backend, kernel, table_set, n=PREP_N):
+    return check_lat_phase1(kernel, prep_batch(), n, lat_phase1_state(backend, kernel, n, table_set), _sb_encodings()[:n])
+
+
+def family_lat_sets(backend, kernel, n=PREP_N):
+    """the two table sets give the same [S]B (limbs may differ) and the same words otherwise"""
+    s1, s2 = (lat_phase1_state(backend, kernel, n, ts) for ts in ("compact", "large"))
+    assert (s1["dig"] == s2["dig"]).all() and (s1["ok"] == s2["ok"]).all() and (s1["pt"][:2] == s2["pt"][:2]).all()
+    for s in range(s1["slots"]):
+        X1, Y1, Z1, _ = _vals([int(v) for v in s1["pt"][2, :, s]])
+        X2, Y2, Z2, _ = _vals([int(v) for v in s2["pt"][2, :, s]])
+        assert (X1 * Z2 - X2 * Z1) % P == 0 and (Y1 * Z2 - Y2 * Z1) % P == 0 and Z1 and Z2, s
+
+
+def family_lat_round_trip(backend, kernel, table_set="compact", n=PREP_N):
+    """phase-1 out -> walk in: the oracle's verdicts"""
+    st = lat_phase1_state(backend, kernel, n, table_set)
+    got = run_lat_walk(backend, kernel, n, st["dig"], st["pt"], st["ok"])
+    assert got[:n].tolist() == [int(q["valid"]) for q in prep_batch()["reqs"][:n]]
+    assert (got[n:] == SENT).all()
+    return got[:n].tolist()

@@ -5,7 +5,10 @@ hc_stage_main runs main_one on an injected state): proves the batch, the
 chosen states, the packing and the checkers here, before the same families
 run on the product's kernels (test_gpu_stage_device.py).  The construction of
 the chosen states is itself checked by plain double-and-add, and every checker
-is shown to raise on a deliberately wrong value."""
+is shown to raise on a deliberately wrong value.  The same for the latency
+kernels' families (phase-1 state out, walk on chosen phase-1 states) on the
+CPU references hc_stage_latency_phase1 / hc_stage_latency_walk, before they
+run on the device (test_gpu_latency_device.py)."""
 import numpy as np
 import pytest
 
@@ -187,3 +190,142 @@ def test_main_checker_rejects_wrong_verdicts(monkeypatch):
     c = dict(next(c for c in cases if not c.get("dead") and c["expect"] == 1 and c["a"] % L))
     c["k"] = (c["k"] + 1) % L
     assert sc.expected_verdict(c) == 0
+
+
+# ---- the latency kernels' families (the latency probes) on the CPU references
+# (hc_stage_latency_phase1 / _walk: references that prove the cases and the
+# checkers, not a build of the quad code, which has none on the CPU)
+KERNELS = ("rtl", "quad")
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_latency_walk_chosen_state(kernel):
+    assert sc.check_lat_walk(B, kernel) >= 700
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
+@pytest.mark.parametrize("n", sc.LAT_WALK_SIZES)
+def test_latency_walk_batch_sizes(kernel, n):
+    sc.check_lat_sizes(B, kernel, n)
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_latency_walk_families_are_all_there(kernel):
+    slots, tally = sc.lat_cases(kernel)
+    live = [c for c in slots if not c.get("dead")]
+    for which in "ab":
+        for accept in (0, 1):
+            assert {c["own"] for c in live if c["tag"].startswith("count %s " % which) and c["expect"] == accept} == \
+                set(range(1, 65))
+    assert sum(tally.dropped.values()) * 50 <= sum(tally.asked.values())
+    assert tally.dropped["count a"] == tally.dropped["count b"] == 0
+    U = sc.LAT_UNIT[kernel]
+    units = [slots[o:o + U] for o in range(0, len(slots) - len(slots) % U, U)]
+    tops = {max([c["word"] for c in u if all(c["alive"])], default=0) for u in units}
+    if kernel == "rtl":
+        assert {0, 1, 2, 3, 4, 5, 7, 8, 9, 63, 64} <= tops
+        assert {t % 4 for t in tops} == {0, 1, 2, 3}
+        for d in range(9):
+            assert any(c["tag"].startswith("bucket %d a" % d) for c in live)
+            assert d in (0, 2, 4, 6, 8) or any(c["tag"].startswith("bucket %d b" % d) for c in live)
+        assert sc.recode4(int("7" * 62 + "8", 16))[0][:63] == [-8] * 63
+        assert {abs(x) for x in sc.recode4(sc.EVERY_BUCKET)[0]} == set(range(9))
+    else:
+        ns = sc.LAT_NS[kernel] // U
+        assert any([max(c["word"] for c in u if all(c["alive"])) for u in units[o:o + ns]] == [1, 16, 33, 64]
+                   for o in range(0, len(units) - ns + 1, ns) if all(any(all(c["alive"]) for c in u) for u in units[o:o + ns]))
+    assert any(c["word"] > c["own"] for c in live) and len(slots) % sc.LAT_NS[kernel]
+    assert {c["alive"] for c in live} >= {(1, 1, 1), (0, 1, 1), (1, 0, 1), (1, 1, 0)}
+    # the spike sits at the first and at the last slot of a unit
+    assert {u.index(c) for u in units for c in u if c["tag"] == "spike 64"} == {0, U - 1}
+    # the three point forms, and limbs at the edge of the bound
+    n, cases, dig, pt, ok = sc.lat_state(kernel)
+    assert n == len(slots) and pt.shape[2] == sc.lat_slots(kernel, n)
+    assert (np.abs(pt[:, 20:30].astype(np.int64)).max(axis=(0, 2)) == np.array(sc.RED)).all()
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_latency_walk_construction_by_double_and_add(kernel):
+    assert sc.check_lat_construction(kernel) >= 100
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
+@pytest.mark.parametrize("table_set", ("compact", "large"))
+def test_latency_phase1_state(kernel, table_set):
+    ab = sc.family_lat_phase1(B, kernel, table_set)
+    assert sum(1 for x in ab if x is not None) >= 540
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
+@pytest.mark.parametrize("n", sc.LAT_P1_SIZES[:-1])
+def test_latency_phase1_batch_sizes(kernel, n):
+    sc.family_lat_phase1(B, kernel, "compact", n)
+    sc.family_lat_phase1(B, kernel, "large", n)
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_latency_table_sets_give_the_same_points(kernel):
+    sc.family_lat_sets(B, kernel)
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_latency_round_trip_matches_the_oracle(kernel):
+    sc.family_lat_round_trip(B, kernel)
+
+
+def test_latency_checkers_reject_wrong_values(monkeypatch):
+    b, n, kernel = sc.prep_batch(), 33, "rtl"
+    good = sc.lat_phase1_state(B, kernel, n, "compact")
+    sc.check_lat_phase1(kernel, b, n, good)
+    ok_slot = next(j for j in range(n) if all(b["reqs"][j]["sides"]))
+    dead = next(j for j in range(n) if not b["reqs"][j]["sides"][1])
+
+    def tampered(key, idx, value, st=good, nn=n):
+        st = _copy(st)
+        st[key][idx] = value
+        _raises(lambda: sc.check_lat_phase1(kernel, b, nn, st))
+
+    tampered("ok", (0, ok_slot), 0)
+    tampered("ok", (1, dead), 1)
+    tampered("ok", (2, 47), 1)                                                 # a slot past the batch marked live
+    tampered("accept", 3, 0)
+    tampered("dig", (0, ok_slot), int(good["dig"][0, ok_slot]) ^ 16)
+    tampered("dig", (16, ok_slot), int(good["dig"][16, ok_slot]) ^ 0x100)
+    tampered("dig", (16, ok_slot), int(good["dig"][16, ok_slot]) + 1)
+    tampered("dig", (3, 40), sc.SENT32)                                        # a word left sentinel
+    tampered("dig", (3, 40), 1)                                                # digits past the batch
+    tampered("pt", (0, 1, ok_slot), int(good["pt"][0, 1, ok_slot]) + 1)        # -A
+    tampered("pt", (1, 35, ok_slot), int(good["pt"][1, 35, ok_slot]) + 1)      # T of -R
+    tampered("pt", (2, 12, ok_slot), int(good["pt"][2, 12, ok_slot]) + 1)      # [S]B
+    tampered("pt", (2, 0, ok_slot), int(good["pt"][2, 0, ok_slot]) + (1 << 28))  # limb bound
+    tampered("pt", (0, 0, dead), 5)                                            # a rejected point is the identity
+    tampered("pt", (2, 10, 45), 0)                                             # past the batch: the identity
+    small = sc.lat_phase1_state(B, kernel, 15, "compact")                      # slot 15 repeats request 14
+    tampered("dig", (1, 15), int(small["dig"][1, 15]) ^ 1, small, 15)
+    tampered("pt", (2, 3, 15), int(small["pt"][2, 3, 15]) + 1, small, 15)
+    neg_a = _copy(good)                                                        # +A where -A belongs
+    neg_a["pt"][0, 0:10, ok_slot] *= -1
+    neg_a["pt"][0, 30:40, ok_slot] *= -1
+    _raises(lambda: sc.check_lat_phase1(kernel, b, n, neg_a))
+    # the walk's checker: a wrong verdict, a byte written past the batch, a dead slot left unwritten
+    real = sc.run_lat_walk
+    nn, cases, dig, pt, ok = sc.lat_state(kernel)
+    base = real(B, kernel, nn, dig, pt, ok)
+    for pick, wrong_value in ((lambda s, c: all(c["alive"]) and c["expect"] == 1, 0),
+                              (lambda s, c: all(c["alive"]) and c["expect"] == 0, 1),
+                              (lambda s, c: s < nn and not all(c["alive"]), sc.SENT), (lambda s, c: s >= nn, 0)):
+        s = next(k for k, c in enumerate(cases) if pick(k, c))
+
+        def wrong(*a, _s=s, _v=wrong_value, **kw):
+            acc = base.copy()
+            acc[_s] = _v
+            return acc
+        monkeypatch.setattr(sc, "run_lat_walk", wrong)
+        _raises(lambda: sc.check_lat_walk(B, kernel))
+    monkeypatch.setattr(sc, "run_lat_walk", real)
+    # the reference walk itself tells -R from R and a digit from its neighbour
+    s = next(k for k, c in enumerate(cases) if all(c["alive"]) and c.get("expect") == 1 and c["a"] > 16)
+    for edit in (lambda d, p: d.__setitem__((0, s), int(d[0, s]) ^ 1), lambda d, p: p.__setitem__((1, slice(0, 10), s), -p[1, 0:10, s])):
+        d2, p2 = dig.copy(), pt.copy()
+        edit(d2, p2)
+        assert base[s] == 1 and real(B, kernel, nn, d2, p2, ok)[s] == 0
