@@ -40,6 +40,8 @@ extern "C" {
 #define EDV_E_NODEV -2 /* no usable gfx950 device in device_mask */
 #define EDV_E_HIP -3   /* HIP runtime error (text: edv_last_error) */
 #define EDV_E_OOM -4   /* device or pinned allocation failed */
+#define EDV_E_BUSY -5  /* edv_trim / edv_release: batches not yet handed over still own caller buffers */
+#define EDV_E_SELFTEST -6 /* edv_self_test / edv_prepare: a verdict differs from libsodium's (text: edv_last_error) */
 
 /*
  * Verify n detached signatures held in HOST memory; synchronous.
@@ -281,6 +283,126 @@ int edv_context_count(void);
  * runs one Node per process.)
  */
 int edv_context_memory(int device, uint64_t out[7]);
+
+/*
+ * ---- Context lifecycle.  A Node is one long-lived process (scripts/
+ * start_plenum_node; several may share a GPU), and its first client request is
+ * authenticated by the same call as every later one (plenum/server/
+ * client_authn.py:83-113).  Without the calls below a device's context (HIP
+ * runtime, streams, the [S]B table set, scratch) is created inside the first
+ * verify, only ever grows, and lives until the process exits.  None of them
+ * changes a verdict or a default; a process that never calls them behaves as
+ * before.  `device` is a logical device index as everywhere else; they return
+ * EDV_E_NODEV for one that does not exist.
+ */
+
+/*
+ * Which [S]B table set the batches of `device` run against; takes effect with
+ * the next batch, builds nothing and frees nothing by itself (edv_trim frees).
+ * Starts as the EDV_SB_TABLES environment variable says (auto / compact /
+ * large; default auto) and survives edv_release.
+ *   EDV_TABLES_AUTO     the compact set (64 MiB); the large one (3 GiB) is built
+ *                       by the first batch of at least 65,536 requests and then
+ *                       used for every batch, small ones included
+ *   EDV_TABLES_COMPACT  always the compact set (built if the context holds only
+ *                       the large one): what a Node verifying prods wants
+ *   EDV_TABLES_LARGE    always the large set (built by the next batch if the
+ *                       context holds only the compact one)
+ * EDV_E_ARG for any other value.  Clears the failed flag of edv_table_state.
+ */
+#define EDV_TABLES_AUTO 0
+#define EDV_TABLES_COMPACT 1
+#define EDV_TABLES_LARGE 2
+int edv_set_table_policy(int device, int policy);
+/*
+ * out[0] the policy, out[1] / out[2] bytes of the compact / large set this
+ * context holds (0: not held; a GPU's sets are shared by its logical devices
+ * and freed when the last context holding one drops it), out[3] 1 if a build
+ * of the large set has failed and is not being retried.  That flag is sticky:
+ * the batch that hit the failure runs on the compact set and returns 0 with
+ * the allocation's error left in edv_last_error, and later batches use the
+ * compact set without another 3 GiB allocation, until edv_set_table_policy,
+ * edv_trim or edv_release clears it.  Works before the context exists (zeros).
+ */
+int edv_table_state(int device, uint64_t out[4]);
+
+/*
+ * Power-on known-answer test: do the kernels on this GPU give libsodium's
+ * verdicts?  (The reference trusts libsodium's own build-time tests; a Node
+ * calls this before it authenticates its first request.)  The cases are part of
+ * the library (RFC 8032 section 7.1 vectors 1-3; a rejecting case for each
+ * strictness rule -- S >= L, small-order R, non-canonical A, small-order A, A
+ * off the curve --, a valid signature over a changed message, a mixed-order A
+ * that libsodium accepts) and run through the synchronous path of
+ * edv_verify_batch, tiled to the smallest batch that takes each family:
+ *   EDV_SELFTEST_RTL       16 requests, the right-to-left latency kernel
+ *   EDV_SELFTEST_TWO_WALK  4,097 requests, the two-walk latency kernel
+ *   EDV_SELFTEST_BATCH     256 requests on the prep + main kernels (the latency
+ *                          path bypassed for this call only; the setting of
+ *                          edv_set_latency_path is neither read nor changed)
+ * on the table set the device's policy picks for such a batch (so never the
+ * large set unless the policy or an earlier batch asked for it).  Creates the
+ * context if needed.  0 when every verdict matches; EDV_E_SELFTEST otherwise,
+ * with the family and the case in edv_last_error; EDV_E_ARG for an empty or
+ * unknown mask; the synchronous path's other errors as they are.
+ */
+#define EDV_SELFTEST_RTL 1u
+#define EDV_SELFTEST_TWO_WALK 2u
+#define EDV_SELFTEST_BATCH 4u
+int edv_self_test(int device, uint32_t families);
+
+/*
+ * Start-up step of a Node (in place of paying for all of it inside the first
+ * prod's verify): creates the context of `device`; builds the table set(s) the
+ * policy uses for batches of up to max_batch requests; grows scratch, input
+ * buffers and pinned staging of the synchronous path -- and of every slot of
+ * the asynchronous path with EDV_PREPARE_ASYNC -- to what such batches need, by
+ * running warm-up batches of max_batch requests (and of 4,096 and the latency
+ * path's limit where those are smaller: one per kernel family) with 512-byte
+ * messages, from pageable and from page-locked memory; then runs edv_self_test
+ * for the families such batches take (RTL up to 4,096 requests, RTL and
+ * TWO_WALK up to the device's latency-path limit, all three above it).  After
+ * it returns 0, a verify of at most max_batch requests whose messages average
+ * at most 512 bytes allocates and builds nothing.  The warm-up batches use
+ * tickets of the asynchronous path's ledger; a caller's ticket whose slot they
+ * reuse is handed over as a later submission would.  Call it again after
+ * changing a setting it depends on (policy, chunk, latency path).
+ * EDV_E_ARG for max_batch 0 or above 2^20 or unknown flags; EDV_E_OOM /
+ * EDV_E_HIP from allocations and launches (a failed build of the large set
+ * included); EDV_E_SELFTEST as edv_self_test.
+ */
+#define EDV_PREPARE_ASYNC 1u
+int edv_prepare(int device, uint64_t max_batch, uint32_t flags);
+
+/*
+ * Gives memory back without giving up the context (a Node after a catch-up
+ * burst of large batches).  Waits for everything queued on the context's
+ * streams, then frees every scratch set, asynchronous slot buffer, pinned
+ * staging and input buffer larger than a batch of keep_batch requests needs
+ * (messages of up to 4,096 bytes allowed for; 0 frees all of them) and drops
+ * the table sets the policy would not pick for a batch of keep_batch in a fresh
+ * context: under EDV_TABLES_AUTO with keep_batch below 65,536 the large set,
+ * which a later batch of 65,536 builds again.  What is freed regrows by use.
+ * EDV_E_BUSY, with nothing changed, while an asynchronous batch of this device
+ * has not been handed over by edv_wait_async / edv_query_async or pipelined
+ * batches have not been synced (edv_pipeline_sync): those still own caller
+ * buffers.  Nothing happens for a device without a context.  Clears the failed
+ * flag of edv_table_state.
+ */
+int edv_trim(int device, uint64_t keep_batch);
+
+/*
+ * Destroys the context of `device` (a Node leaving a GPU, or rebuilding its
+ * context after an EDV_E_HIP): same wait and EDV_E_BUSY rule as edv_trim, then
+ * every stream, event, device and pinned buffer goes and the table sets are
+ * dropped; edv_context_count falls by one and edv_context_memory reports
+ * zeros.  The device's settings (edv_set_*) are kept, and so is the ticket
+ * count of the asynchronous path: a ticket issued before the release still
+ * answers as settled (or failed), never as a later batch.  Device memory from
+ * edv_dev_alloc and streams obtained from edv_stream are the caller's to free
+ * and forget first.  The next call on the device creates a fresh context.
+ */
+int edv_release(int device);
 
 /*
  * The shard split edv_verify_batch uses (host only, no GPU needed): bounds[0..g]

@@ -148,7 +148,7 @@ int edv_probe_math(int device, int op, const void *in, uint64_t in_stride, void 
  *
  * edv_probe_prep_state: [bucket kernels,] prep kernel over n <= EDV_STAGE_CAP
  * requests (sigs n x 64, pks n x 32, msgs, msg_off n + 1 absolute offsets into
- * msgs) against table set `set` (EDV_TABLES_COMPACT / _LARGE, built if the GPU
+ * msgs) against table set `set` (EDV_TABLE_SET_COMPACT / _LARGE, built if the GPU
  * has not built it yet), sides side0 .. side0 + nsides - 1 in one launch, or
  * with EDV_STAGE_SPLIT (side0 = 0, nsides = 3) as the split pipeline's two
  * launches, 0 / 1 then 1 / 2.  EDV_STAGE_BUCKETS runs the length-bucket
@@ -165,9 +165,9 @@ int edv_probe_math(int device, int op, const void *in, uint64_t in_stride, void 
  *
  * edv_probe_table: entries (t, j) = tj[2 k], tj[2 k + 1] of a device table as
  * the context's kernels read it, 32 words each (y+x, y-x, 2dxy limbs, 2 words
- * of padding): EDV_TABLES_COMPACT (16 x 32,769: j x 2^(16 t) B),
- * EDV_TABLES_LARGE (12 x 2,097,153: j x 2^(22 t) B; builds the 3 GiB set if
- * this GPU has none) or EDV_TABLES_COMB (the signer's 32 x 129: j x 256^t B).
+ * of padding): EDV_TABLE_SET_COMPACT (16 x 32,769: j x 2^(16 t) B),
+ * EDV_TABLE_SET_LARGE (12 x 2,097,153: j x 2^(22 t) B; builds the 3 GiB set if
+ * this GPU has none) or EDV_TABLE_SET_COMB (the signer's 32 x 129: j x 256^t B).
  * Device-side copies only, no kernel but a missing table's build.
  */
 #define EDV_STAGE_CAP 4096
@@ -175,9 +175,9 @@ int edv_probe_math(int device, int op, const void *in, uint64_t in_stride, void 
 #define EDV_STAGE_BUCKETS 1u
 #define EDV_STAGE_SPLIT 2u
 #define EDV_STAGE_PRIO 4u
-#define EDV_TABLES_COMPACT 0
-#define EDV_TABLES_LARGE 1
-#define EDV_TABLES_COMB 2
+#define EDV_TABLE_SET_COMPACT 0
+#define EDV_TABLE_SET_LARGE 1
+#define EDV_TABLE_SET_COMB 2
 int edv_probe_prep_state(int device, const uint8_t *sigs, const uint8_t *pks, const uint8_t *msgs,
                          const uint64_t *msg_off, uint64_t n, int set, int side0, int nsides, uint32_t flags,
                          uint32_t *dig, uint8_t *alive, int32_t *atab, int32_t *rtab, uint32_t *perm,
@@ -207,7 +207,7 @@ int edv_probe_table(int device, int set, const int32_t *tj, uint64_t n, int32_t 
  *   ok    G x 3 x NS bytes      ok[(g 3 + k) NS + j]: side k (0 hash, 1 A, 2 R) passed
  *
  * edv_probe_latency_phase1: phase1<BITS, NS> over n <= EDV_STAGE_CAP requests
- * against table set `set` (EDV_TABLES_COMPACT / _LARGE), exactly as the
+ * against table set `set` (EDV_TABLE_SET_COMPACT / _LARGE), exactly as the
  * product kernel runs it; after the barrier each workgroup copies its L.dig,
  * L.pt and L.ok out.  dig, pt, ok and accept (n bytes: phase 1 writes no
  * verdict) are filled with EDV_STAGE_SENTINEL bytes first.

@@ -9,6 +9,8 @@
 #include "edv_verify_core.h"
 #include "edv_sha256.h"
 #include "edv_ledger.h"
+#include "edv_tables.h"
+#include "edv_selftest_cases.h"
 #include "edv_probe_ops.h"
 
 using namespace edv;
@@ -493,6 +495,26 @@ void hc_ledger(int64_t n, const int64_t* failed, int nf, const int64_t* queries,
   for (int64_t i = 0; i < n; i++) l.issue();
   for (int k = 0; k < nf; k++) l.fail(failed[k]);
   for (int k = 0; k < nq; k++) out[k] = l.settled(queries[k]);
+}
+// the table-set decision the runtime makes per batch (edv_tables.h): out = use, build, failed
+void hc_choose_tables(int policy, uint64_t n, int have_compact, int have_large, int failed, int* out3) {
+  const TableChoice c = choose_tables(policy, n, have_compact != 0, have_large != 0, failed != 0);
+  out3[0] = c.use;
+  out3[1] = c.build;
+  out3[2] = c.failed ? 1 : 0;
+}
+// the known answers of edv_self_test (edv_selftest_cases.h), as the library holds them
+int hc_selftest_count() { return kSelfTestCases; }
+int hc_selftest_case(int i, uint8_t* sig64, uint8_t* pk32, uint8_t* msg, uint64_t* mlen, int* accept, int* rule) {
+  if (i < 0 || i >= kSelfTestCases) return -1;
+  const SelfTestCase& t = selftest_cases()[i];
+  memcpy(sig64, t.sig, 64);
+  memcpy(pk32, t.pk, 32);
+  memcpy(msg, t.msg, sizeof t.msg);
+  *mlen = t.mlen;
+  *accept = t.accept;
+  *rule = t.rule;
+  return int(sizeof t.msg);
 }
 // windows the packed radix-2^kAWin digits need (the prep kernel's per-lane count)
 int hc_digits_windows(const uint32_t* d8) { return digits5_windows(d8); }

@@ -92,6 +92,7 @@ int edv_profile_batch_dev_flush(const uint8_t* d_sigs, const uint8_t* d_pks, con
   if ((err = grow_state(*c, n))) return err;
   const bool bucket = bucketing_enabled(*c, 0);
   VerifyArgs va = make_args(*c, c->st, d_sigs, d_pks, d_msgs, d_msg_off, msg_base, d_accept, bucket, 0, n);
+  if (!va.btab) return no_tables(*c);
   va.n = n;
   uint32_t* hist = bucket_ctr(c->st, 0);
   const unsigned blocks = unsigned((n + kBlock - 1) / kBlock);
@@ -161,6 +162,7 @@ int edv_profile_prep_sides(const uint8_t* d_sigs, const uint8_t* d_pks, const ui
   if (n == 0 || n > c->chunk || iters <= 0) return set_err(EDV_E_ARG, "profile needs 0 < n <= chunk, iters > 0");
   if ((err = grow_state(*c, n))) return err;
   VerifyArgs va = make_args(*c, c->st, d_sigs, d_pks, d_msgs, d_msg_off, msg_base, d_accept, false, 0, n);
+  if (!va.btab) return no_tables(*c);
   va.n = n;
   const unsigned blocks = unsigned((n + kBlock - 1) / kBlock);
   Events ev;
@@ -234,7 +236,7 @@ int edv_probe_prep_state(int device, const uint8_t* sigs, const uint8_t* pks, co
                          uint32_t* dig, uint8_t* alive, int32_t* atab, int32_t* rtab, uint32_t* perm, uint8_t* accept,
                          uint64_t* cap_out) {
   g_err.clear();
-  if (set != EDV_TABLES_COMPACT && set != EDV_TABLES_LARGE) return set_err(EDV_E_ARG, "prep probe: unknown table set");
+  if (set != EDV_TABLE_SET_COMPACT && set != EDV_TABLE_SET_LARGE) return set_err(EDV_E_ARG, "prep probe: unknown table set");
   if (side0 < 0 || nsides < 1 || side0 > 2 || nsides > 3 || side0 + nsides > 3)
     return set_err(EDV_E_ARG, "prep probe: sides out of range");
   if (flags & ~(EDV_STAGE_BUCKETS | EDV_STAGE_SPLIT)) return set_err(EDV_E_ARG, "prep probe: unknown flag");
@@ -256,7 +258,7 @@ int edv_probe_prep_state(int device, const uint8_t* sigs, const uint8_t* pks, co
   if (cl.err) return cl.err;
   DevCtx* c = cl.c;
   int err = 0;
-  const SbShape sh = set == EDV_TABLES_LARGE ? sb_large() : sb_compact();
+  const SbShape sh = set == EDV_TABLE_SET_LARGE ? sb_large() : sb_compact();
   const int32_t* tables = shared_tables(c->phys, sh, c->stream, &err);  // this GPU's set, built on first use
   if (!tables) return err;
   StageBuf dsigs, dpks, dmsgs, doff, dacc, datab, drtab, ddig, dalive, dperm, dctr;
@@ -357,14 +359,14 @@ int edv_probe_main_state(int device, uint64_t n, uint64_t cap, const uint32_t* d
 
 int edv_probe_table(int device, int set, const int32_t* tj, uint64_t n, int32_t* out) {
   g_err.clear();
-  if (set != EDV_TABLES_COMPACT && set != EDV_TABLES_LARGE && set != EDV_TABLES_COMB)
+  if (set != EDV_TABLE_SET_COMPACT && set != EDV_TABLE_SET_LARGE && set != EDV_TABLE_SET_COMB)
     return set_err(EDV_E_ARG, "table probe: unknown table set");
   if (n > (uint64_t(1) << 20)) return set_err(EDV_E_ARG, "table probe: at most 2^20 entries");
   if (n == 0) return 0;
   if (!tj || !out) return set_err(EDV_E_ARG, "table probe: null buffer");
-  const SbShape sh = set == EDV_TABLES_LARGE ? sb_large() : sb_compact();
-  const int rows = set == EDV_TABLES_COMB ? kCombRows : sh.tables;
-  const int entries = set == EDV_TABLES_COMB ? kCombEntries : sh.entries;
+  const SbShape sh = set == EDV_TABLE_SET_LARGE ? sb_large() : sb_compact();
+  const int rows = set == EDV_TABLE_SET_COMB ? kCombRows : sh.tables;
+  const int entries = set == EDV_TABLE_SET_COMB ? kCombEntries : sh.entries;
   for (uint64_t k = 0; k < n; k++)
     if (tj[2 * k] < 0 || tj[2 * k] >= rows || tj[2 * k + 1] < 0 || tj[2 * k + 1] >= entries)
       return set_err(EDV_E_ARG, "table probe: entry out of range");
@@ -373,7 +375,7 @@ int edv_probe_table(int device, int set, const int32_t* tj, uint64_t n, int32_t*
   DevCtx* c = cl.c;
   int err = 0;
   const int32_t* table;
-  if (set == EDV_TABLES_COMB) {
+  if (set == EDV_TABLE_SET_COMB) {
     if ((err = ensure_comb(*c))) return err;
     table = c->comb;
   } else if (!(table = shared_tables(c->phys, sh, c->stream, &err))) {
@@ -405,7 +407,7 @@ int edv_probe_latency_phase1(int device, int kernel, int set, const uint8_t* sig
   g_err.clear();
   const uint64_t ns = uint64_t(probe_latency_sigs(kernel));
   if (!ns) return set_err(EDV_E_ARG, "latency phase-1 probe: unknown kernel");
-  if (set != EDV_TABLES_COMPACT && set != EDV_TABLES_LARGE)
+  if (set != EDV_TABLE_SET_COMPACT && set != EDV_TABLE_SET_LARGE)
     return set_err(EDV_E_ARG, "latency phase-1 probe: unknown table set");
   if (n > EDV_STAGE_CAP) return set_err(EDV_E_ARG, "latency phase-1 probe: at most EDV_STAGE_CAP requests");
   if (n == 0) return 0;
@@ -420,7 +422,7 @@ int edv_probe_latency_phase1(int device, int kernel, int set, const uint8_t* sig
   if (cl.err) return cl.err;
   DevCtx* c = cl.c;
   int err = 0;
-  const SbShape sh = set == EDV_TABLES_LARGE ? sb_large() : sb_compact();
+  const SbShape sh = set == EDV_TABLE_SET_LARGE ? sb_large() : sb_compact();
   const int32_t* tables = shared_tables(c->phys, sh, c->stream, &err);  // this GPU's set, built on first use
   if (!tables) return err;
   const uint64_t slots = (n + ns - 1) / ns * ns;

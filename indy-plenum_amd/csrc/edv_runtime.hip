@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <atomic>
 #include <mutex>
+#include <new>
 #include <thread>
 #include <unistd.h>
 #include <vector>
@@ -19,6 +20,8 @@
 #include "edv_kernels.h"
 #include "edv_launch.h"
 #include "edv_ledger.h"
+#include "edv_tables.h"
+#include "edv_selftest_cases.h"
 #include "../../include/edv.h"
 
 using namespace edv;
@@ -52,6 +55,10 @@ struct DevBuf {
     cap = bytes;
     return 0;
   }
+  void release() {  // the caller guarantees that nothing queued still uses it (edv_trim, edv_release)
+    if (p) (void)hipFree(p);
+    p = nullptr; cap = 0;
+  }
 };
 
 // Pinned (page-locked, portable) host memory: staging of pageable inputs
@@ -74,6 +81,10 @@ struct PinnedBuf {
       dev = nullptr;
     }
     return 0;
+  }
+  void release() {
+    if (p) (void)hipHostFree(p);
+    p = nullptr; dev = nullptr; cap = 0;
   }
 };
 
@@ -135,6 +146,10 @@ struct ChunkBufs {
     return 0;
   }
   uint64_t bytes() const { return atab.cap + rtab.cap + dig.cap + alive.cap + perm.cap + bucket_ctr.cap; }
+  void release() {
+    for (DevBuf* b : {&atab, &rtab, &dig, &alive, &perm, &bucket_ctr}) b->release();
+    cap = 0;
+  }
 };
 
 struct DevCtx {
@@ -145,8 +160,12 @@ struct DevCtx {
   int dev = -1;                    // logical device (edv_* device index)
   int phys = -1;                   // HIP device it runs on
   hipStream_t stream = nullptr;    // the library stream (edv_stream)
-  const int32_t* sb_compact = nullptr;  // the GPU's [S]B table sets (shared_tables), when built
+  const int32_t* sb_compact = nullptr;  // the GPU's [S]B table sets this context holds (shared_tables / drop_tables)
   const int32_t* sb_large = nullptr;
+  int policy = kTablesAuto;        // which set a batch uses (edv_set_table_policy; EDV_SB_TABLES at start)
+  bool sb_failed = false;          // a build of the large set failed and is not retried (edv_table_state)
+  int sb_err = 0;                  // why pick_tables had no set to give
+  bool env_read = false;           // EDV_CHUNK applies to the first context only: edv_release keeps the settings
   int32_t* comb = nullptr;         // signer comb table, built on first edv_sign_* call
   uint64_t chunk = kChunkDefault;  // EDV_CHUNK overrides (tests exercise chunk seams)
   int length_buckets = 2;          // 0 never, 1 always, 2 auto (edv_set_length_buckets)
@@ -220,7 +239,8 @@ int g_ndev = -1;
 
 // ---- the [S]B tables (the prep kernel's R side): one copy per GPU and shape
 // in a process, shared by every logical device (EDV_VIRTUAL_DEVICES) mapped
-// onto that GPU.  Which shapes a context builds (EDV_SB_TABLES):
+// onto that GPU.  Which set a batch runs against is the device's policy
+// (edv_set_table_policy, edv_tables.h), EDV_SB_TABLES until it is set:
 //   auto (default)  the compact set (64 MiB) at context creation; the large
 //                   set (3 GiB, 4 fewer additions per verify, +1 % at C2) once
 //                   a batch of at least kLargeTablesMin requests arrives -- a
@@ -228,15 +248,16 @@ int g_ndev = -1;
 //                   allocates it (footprint)
 //   compact         never the large set
 //   large           the large set at context creation (the compact one never)
-// A failed allocation of the large set leaves the compact one in use.
-constexpr uint64_t kLargeTablesMin = 65536;  // one wave per SIMD of a whole MI355X
-enum SbPolicy { kSbAuto, kSbCompact, kSbLarge };
-SbPolicy sb_policy() {
-  static const SbPolicy p = [] {
+// A failed allocation of the large set leaves the compact one in use and is
+// not tried again (DevCtx::sb_failed).  A context holds the sets it has used
+// (DevCtx::sb_compact / sb_large); a set is freed when its last holder drops
+// it (edv_trim, edv_release).
+int sb_policy() {
+  static const int p = [] {
     const char* e = getenv("EDV_SB_TABLES");
-    if (e && !strcmp(e, "compact")) return kSbCompact;
-    if (e && !strcmp(e, "large")) return kSbLarge;
-    return kSbAuto;
+    if (e && !strcmp(e, "compact")) return int(kTablesCompact);
+    if (e && !strcmp(e, "large")) return int(kTablesLarge);
+    return int(kTablesAuto);
   }();
   return p;
 }
@@ -245,15 +266,21 @@ struct SbSet {
   int bits;
   int32_t* p;
   uint64_t bytes;
+  int holders;
 };
 std::mutex g_sb_mu;
 std::vector<SbSet> g_sb;
-// The table set of shape sh on GPU phys (current device = phys), built on
-// first use; nullptr (with the error set) if it cannot be allocated or built.
+// One more hold on the table set of shape sh on GPU phys (current device =
+// phys), built on first use; nullptr (with the error set) if it cannot be
+// allocated or built.  Contexts pair it with drop_tables; the measurement
+// build's probes do not, so a set they have used stays for the process.
 const int32_t* shared_tables(int phys, SbShape sh, hipStream_t s, int* err) {
   std::lock_guard<std::mutex> lk(g_sb_mu);
-  for (const SbSet& t : g_sb)
-    if (t.phys == phys && t.bits == sh.bits) return t.p;
+  for (SbSet& t : g_sb)
+    if (t.phys == phys && t.bits == sh.bits) {
+      t.holders++;
+      return t.p;
+    }
   const uint64_t bytes = sb_alloc_bytes(sh);
   int32_t* p = nullptr;
   if (hipMalloc(&p, bytes) != hipSuccess) {
@@ -268,8 +295,22 @@ const int32_t* shared_tables(int phys, SbShape sh, hipStream_t s, int* err) {
     *err = set_err(EDV_E_HIP, "[S]B table build", e);
     return nullptr;
   }
-  g_sb.push_back({phys, sh.bits, p, bytes});
+  g_sb.push_back({phys, sh.bits, p, bytes, 1});
   return p;
+}
+// Gives one hold back; the last one frees the set (current device = phys, and
+// nothing queued by the caller still reads it).
+void drop_tables(int phys, SbShape sh) {
+  std::lock_guard<std::mutex> lk(g_sb_mu);
+  for (size_t k = 0; k < g_sb.size(); k++) {
+    SbSet& t = g_sb[k];
+    if (t.phys != phys || t.bits != sh.bits) continue;
+    if (--t.holders <= 0) {
+      (void)hipFree(t.p);
+      g_sb.erase(g_sb.begin() + k);
+    }
+    return;
+  }
 }
 uint64_t shared_tables_bytes(int phys) {
   std::lock_guard<std::mutex> lk(g_sb_mu);
@@ -299,6 +340,7 @@ int device_count_locked() {
     g_ctx[i] = new DevCtx();
     g_ctx[i]->dev = i;
     g_ctx[i]->phys = n > 0 ? i % n : 0;
+    g_ctx[i]->policy = sb_policy();
   }
   return logical;
 }
@@ -330,13 +372,14 @@ int ctx_init(DevCtx& c) {
     if (!s.done) HIPOK(hipEventCreateWithFlags(&s.done, hipEventDisableTiming), "event");
   }
   if (!c.st_done) HIPOK(hipEventCreateWithFlags(&c.st_done, hipEventDisableTiming), "event");
-  if (const char* e = getenv("EDV_CHUNK")) {
+  if (const char* e = c.env_read ? nullptr : getenv("EDV_CHUNK")) {
     const uint64_t v = strtoull(e, nullptr, 10);
     if (v >= kBlock && v <= (uint64_t(1) << 24)) c.chunk = (v / kBlock) * kBlock;
   }
-  // the scratch grows by use (ChunkBufs); the [S]B tables: see sb_policy
+  c.env_read = true;
+  // the scratch grows by use (ChunkBufs); the [S]B tables: the device's policy (pick_tables)
   int err = 0;
-  if (sb_policy() == kSbLarge) {
+  if (c.policy == kTablesLarge) {
     if (!c.sb_large && !(c.sb_large = shared_tables(c.phys, sb_large(), c.stream, &err))) return err;
   } else if (!c.sb_compact && !(c.sb_compact = shared_tables(c.phys, sb_compact(), c.stream, &err))) {
     return err;
@@ -376,23 +419,37 @@ int phys_of(int device, int* phys) {
   return 0;
 }
 
-// The [S]B table set a batch of n requests runs against (sb_policy): the
-// large set once built (or once a batch this large asks for it), else the
-// compact one.  Caller holds c.mu; the current device is c.phys.
+// The [S]B table set a batch of n requests runs against: choose_tables
+// (edv_tables.h) over the device's policy and the sets the context holds,
+// building the one it asks for.  A failed build of the large set is kept in
+// edv_last_error, marks the context (sb_failed: no further 3 GiB hipMalloc per
+// batch) and leaves the batch on the compact set.  *t stays null, with the
+// code in c.sb_err, only when no set can be had at all (no_tables).  Caller
+// holds c.mu; the current device is c.phys.
 void pick_tables(DevCtx& c, uint64_t n, const int32_t** t, SbShape* sh) {
-  if (!c.sb_large && sb_policy() == kSbAuto && n >= kLargeTablesMin) {
-    int err = 0;
-    c.sb_large = shared_tables(c.phys, sb_large(), c.stream, &err);  // stays compact if this fails
-    if (!c.sb_large) g_err.clear();
-  }
-  if (c.sb_large) {
-    *t = c.sb_large;
-    *sh = sb_large();
-  } else {
-    *t = c.sb_compact;
-    *sh = sb_compact();
+  *t = nullptr;
+  for (int round = 0; round < 2; round++) {
+    const TableChoice ch = choose_tables(c.policy, n, c.sb_compact != nullptr, c.sb_large != nullptr, c.sb_failed);
+    c.sb_failed = ch.failed;
+    const bool large = ch.use == kSetLarge;
+    const int32_t*& held = large ? c.sb_large : c.sb_compact;
+    if (ch.build != kSetNone) {
+      int err = 0;
+      held = shared_tables(c.phys, large ? sb_large() : sb_compact(), c.stream, &err);
+      if (!held) {
+        c.sb_err = err;
+        if (!large) return;
+        c.sb_failed = true;  // ask again: the compact set
+        continue;
+      }
+    }
+    *t = held;
+    *sh = large ? sb_large() : sb_compact();
+    return;
   }
 }
+// The error of a launch for which pick_tables had no table set.
+int no_tables(const DevCtx& c) { return c.sb_err ? c.sb_err : set_err(EDV_E_HIP, "no [S]B table set"); }
 
 // Grow the context's ordinary chunk scratch to `need` signatures (at most one
 // chunk's worth is ever used at once), after every queued user of it is done.
@@ -501,6 +558,7 @@ int launch_quad(DevCtx& c, DevBuf& qtab, const uint8_t* d_sigs, const uint8_t* d
   va.n = n;
   va.accept = d_acc;
   pick_tables(c, n, &va.btab, &va.sb);
+  if (!va.btab) return no_tables(c);
 #ifdef EDV_MEASURE_NO_VERIFY
   HIPOK(hipMemsetAsync(d_acc, 1, n, s), "memset accept");  // measurement build: see launch_main
   return 0;
@@ -527,6 +585,7 @@ int launch(DevCtx& c, const uint8_t* d_sigs, const uint8_t* d_pks, const uint8_t
   if ((err = grow_state(c, n))) return err;
   HIPOK(hipStreamWaitEvent(s, c.st_done, 0), "wait scratch");
   VerifyArgs va = make_args(c, c.st, d_sigs, d_pks, d_msgs, d_off, msg_base, d_accept, bucket, 0, n);
+  if (!va.btab) return no_tables(c);
   for (uint64_t base = 0; base < n; base += c.chunk) {
     va.base = base;
     va.n = (n - base) < c.chunk ? (n - base) : c.chunk;
@@ -546,6 +605,7 @@ int launch_own(DevCtx& c, ChunkBufs& cb, const uint8_t* d_sigs, const uint8_t* d
   if (n == 0) return 0;
   const bool bucket = bucketing_enabled(c, flags);
   VerifyArgs va = make_args(c, cb, d_sigs, d_pks, d_msgs, d_off, msg_base, d_accept, bucket, 0, n);
+  if (!va.btab) return no_tables(c);
   const uint64_t step = c.chunk < cb.cap ? c.chunk : cb.cap;
   int err;
   for (uint64_t base = 0; base < n; base += step) {
@@ -593,6 +653,7 @@ int launch_pipelined(DevCtx& c, const uint8_t* d_sigs, const uint8_t* d_pks, con
       if (cb.ensure(cn, c.chunk)) return EDV_E_OOM;
     }
     VerifyArgs va = make_args(c, cb, d_sigs, d_pks, d_msgs, d_off, msg_base, d_accept, bucket, 0, n);
+    if (!va.btab) return no_tables(c);
     va.base = base;
     va.n = cn;
     if (c.pending[b]) HIPOK(hipStreamWaitEvent(c.sp, c.main_done[b], 0), "wait");
@@ -961,6 +1022,7 @@ int run_shard_fields(DevCtx& c, const uint8_t* sigs, const uint8_t* pks, const u
   const bool zc_acc = zc != nullptr;
   // the point sides first: they need only what has just been queued
   VerifyArgs va = make_args(c, c.st, d_sigs, d_pks, d_msgs, d_off, mbase, d_acc, bucket, 0, n);
+  if (!va.btab) return no_tables(c);
   va.n = n;
   HIPOK(hipStreamWaitEvent(s0, c.part_copied[0], 0), "wait copy");
   if (bucket && (err = launch_buckets(bucket_ctr(c.st, 0), va, d_off, s0))) return err;
@@ -990,7 +1052,7 @@ int run_shard_fields(DevCtx& c, const uint8_t* sigs, const uint8_t* pks, const u
     const hipStream_t hk = K == 1 ? s0 : c.hs[1 + k % (kQ - 1)];
     // requests [rb[k], rb[k+1]) of the shard: scratch slots and request index
     // both start at rb[k] (a bucketed shard is one slice, over the permutation)
-    VerifyArgs vh = make_args(c, c.st, d_sigs, d_pks, d_msgs, d_off, mbase, d_acc, bucket, rb[k]);
+    VerifyArgs vh = make_args(c, c.st, d_sigs, d_pks, d_msgs, d_off, mbase, d_acc, bucket, rb[k], n);
     vh.base = rb[k];
     vh.n = rb[k + 1] - rb[k];
     vh.side0 = 0;
@@ -1057,11 +1119,12 @@ int run_shard_quad(DevCtx& c, const uint8_t* sigs, const uint8_t* pks, const uin
 // (known from the argument check), 0 = not, so the shard is scanned for it;
 // -1 = the offsets are not checked yet (a large one-shard call: the field path
 // checks them while its first copy runs, the other paths first thing).
+// no_latency: this call takes the batch kernels whatever c.quad_max is (edv_self_test).
 int run_shard(DevCtx& c, const uint8_t* sigs, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, uint64_t lo,
-              uint64_t hi, uint8_t* accept, int uniform) {
+              uint64_t hi, uint8_t* accept, int uniform, bool no_latency = false) {
   const uint64_t n = hi - lo;
   if (n == 0) return 0;
-  if (n <= c.quad_max) return run_shard_quad(c, sigs, pks, msgs, off, lo, hi, accept);
+  if (!no_latency && n <= c.quad_max) return run_shard_quad(c, sigs, pks, msgs, off, lo, hi, accept);
   // A shard that fits one chunk is one sub-batch (the field path): split 2 or
   // 4 ways at 64k it measured 1.6x / 1.9x slower (profiles/r02/e2e_probe_s4.json),
   // as a 16k sub-batch still takes a whole batch's latency at one wave per
@@ -1144,6 +1207,7 @@ int run_shard(DevCtx& c, const uint8_t* sigs, const uint8_t* pks, const uint8_t*
     const bool bucket = bucketing_enabled(c, flags);
     VerifyArgs va = make_args(c, c.st, d_sigs + 64 * (a - lo), d_pks + 32 * (a - lo), d_msgs, d_o, mbase,
                               d_acc + (a - lo), bucket, uint64_t(q) * pmax, n);
+    if (!va.btab) return no_tables(c);
     va.n = cnt;
     if ((err = launch_prep(bucket_ctr(c.st, q), va, d_o, bucket, s)) || (err = launch_main(va, s))) return err;
     HIPOK(hipMemcpyAsync(h_acc + (a - lo), d_acc + (a - lo), cnt, hipMemcpyDeviceToHost, s), "d2h accept");
@@ -1542,6 +1606,263 @@ int check_dev_align(const void* d_sigs, const void* d_pks, const void* d_off) {
   return 0;
 }
 
+
+// ---- context lifecycle (edv_prepare, edv_self_test, edv_trim, edv_release)
+// An asynchronous batch not yet handed over, or a pipelined batch not yet
+// synced, still owns caller buffers: the context cannot be trimmed or released.
+bool ctx_busy(const DevCtx& c) {
+  for (const auto& s : c.as)
+    if (s.ticket >= 0) return true;
+  return c.pending[0] || c.pending[1];
+}
+
+// Message bytes per request the warm-up batches of edv_prepare carry, and the
+// most a buffer may hold per request of keep_batch and still survive edv_trim.
+constexpr uint64_t kPrepareMsgBytes = 512;
+constexpr uint64_t kTrimMsgBytes = 4096;
+constexpr uint64_t kPrepareMax = uint64_t(1) << 20;  // a warm-up batch is built in host memory: 0.7 GB here
+
+// Free what is larger than a batch of `keep` requests needs (0: everything),
+// after the context is drained.  Caller holds c.mu; the current device is c.phys.
+void trim_buffers(DevCtx& c, uint64_t keep) {
+  const uint64_t k = keep;
+  uint64_t slots = 0;  // the ChunkBufs capacity such a batch grows a set to (ChunkBufs::ensure)
+  if (k) {
+    slots = 4096;
+    while (slots < k && slots < c.chunk) slots <<= 1;
+    if (slots > c.chunk) slots = c.chunk;
+  }
+  const uint64_t packed = k ? 104 * k + 8 + 4096 : 0;               // signatures | keys | offsets in one span
+  const uint64_t blob = k ? packed + k * kTrimMsgBytes + 64 : 0;     // ... and the messages
+  const uint64_t pinned = blob + blob / 4 + (k ? 4096 : 0);          // PinnedBuf's headroom
+  const uint64_t kq = k < kQuadMaxLimit ? k : kQuadMaxLimit;
+  const uint64_t qtab = kq > kRtlMax ? (kq + 63) / 64 * 64 * kQSigWords * 4 : 0;
+  auto dev = [](DevBuf& b, uint64_t limit) {
+    if (b.cap > limit) b.release();
+  };
+  auto pin = [](PinnedBuf& b, uint64_t limit) {
+    if (b.cap > limit) b.release();
+  };
+  auto set = [&](ChunkBufs& b) {
+    if (b.cap > slots) b.release();
+  };
+  set(c.st);
+  set(c.pst[0]);
+  set(c.pst[1]);
+  dev(c.sigs, 64 * k);
+  dev(c.pks, 32 * k);
+  dev(c.msgs, k * kTrimMsgBytes + 64);
+  dev(c.off, k ? 8 * (k + k / (c.chunk / 2 ? c.chunk / 2 : 1) + 2) : 0);
+  dev(c.acc, k);
+  dev(c.fblob, packed);
+  dev(c.qblob, blob);
+  dev(c.qtab, qtab);
+  pin(c.qstage, pinned);
+  pin(c.acc_host, k + k / 4 + (k ? 4096 : 0));
+  for (int q = 0; q < kQ; q++) pin(c.stage[q], pinned);
+  for (auto& a : c.as) {
+    set(a.cb);
+    dev(a.sigs, 64 * k);
+    dev(a.pks, 32 * k);
+    dev(a.msgs, blob);  // the latency path packs the whole batch here
+    dev(a.off, k ? 8 * (k + 1) : 0);
+    dev(a.acc, k);
+    dev(a.dig, 32 * k);
+    dev(a.qtab, qtab);
+    pin(a.stage, pinned);
+    pin(a.acc_host, k + k / 4 + (k ? 4096 : 0));
+    pin(a.dig_host, 32 * k + 8 * k + (k ? 4096 : 0));
+  }
+}
+
+// Drop the holds on the table sets a batch of `keep` requests would not run
+// against under the device's policy in a fresh context (under `auto` below
+// kLargeTablesMin: the large set); all = both.  Caller holds c.mu, the context
+// is drained, the current device is c.phys.
+void trim_tables(DevCtx& c, uint64_t keep, bool all) {
+  const int keepset = all ? int(kSetNone) : choose_tables(c.policy, keep, false, false, false).use;
+  if (c.sb_large && keepset != kSetLarge) {
+    drop_tables(c.phys, sb_large());
+    c.sb_large = nullptr;
+  }
+  // the compact set goes only when the set used instead is there
+  if (c.sb_compact && (all || (keepset == kSetLarge && c.sb_large))) {
+    drop_tables(c.phys, sb_compact());
+    c.sb_compact = nullptr;
+  }
+}
+
+// Back to the state before ctx_init: no stream, event, buffer or table hold.
+// The settings (chunk, policy, latency path, ...) and the ledger stay.
+void ctx_destroy(DevCtx& c) {
+  trim_buffers(c, 0);
+  trim_tables(c, 0, true);
+  if (c.comb) (void)hipFree(c.comb);
+  c.comb = nullptr;
+  auto ev = [](hipEvent_t& e) {
+    if (e) (void)hipEventDestroy(e);
+    e = nullptr;
+  };
+  auto st = [](hipStream_t& x) {
+    if (x) (void)hipStreamDestroy(x);
+    x = nullptr;
+  };
+  for (int q = 0; q < kQ; q++) {
+    st(c.hs[q]);
+    ev(c.hs_staged[q]);
+    ev(c.hs_end[q]);
+    ev(c.part_copied[q]);
+    ev(c.part_prepped[q]);
+  }
+  for (int k = 0; k < kSlices; k++) {
+    ev(c.slice_copied[k]);
+    ev(c.slice_hashed[k]);
+  }
+  for (auto& a : c.as) {
+    st(a.st);
+    ev(a.copied);
+    ev(a.done);
+    a.ticket = -1;
+    a.accept = a.digests = nullptr;
+    a.n = 0;
+  }
+  for (int b = 0; b < 2; b++) {
+    ev(c.prep_done[b]);
+    ev(c.main_done[b]);
+    ev(c.perm_done[b]);
+    c.pending[b] = false;
+  }
+  ev(c.inputs_ready);
+  ev(c.st_done);
+  st(c.sp);
+  st(c.sm);
+  st(c.hcp);
+  st(c.hac);
+  st(c.stream);
+  c.pipe_ready = false;
+  c.next = 0;
+  c.ready = false;
+  c.live.store(false);
+}
+
+// A batch of n requests laid out as edv_verify_batch takes it, in one block
+// (signatures | keys | offsets | messages | verdicts | digests), in pageable
+// or page-locked memory: the self-test's cases in turn with their own messages
+// and verdicts (pad == 0), or the cases' signatures and keys over `pad` zero
+// bytes each (a warm-up batch: its verdicts mean nothing).
+struct KatBatch {
+  std::vector<uint8_t> heap;
+  uint8_t* base = nullptr;
+  bool pinned = false;
+  uint64_t n = 0;
+  uint8_t *sigs = nullptr, *pks = nullptr, *msgs = nullptr, *accept = nullptr, *digests = nullptr;
+  uint64_t* off = nullptr;
+  std::vector<uint8_t> want;
+  int build(uint64_t count, uint64_t pad, bool pin) {
+    n = count;
+    pinned = pin;
+    const SelfTestCase* k = selftest_cases();
+    uint64_t mbytes = 0;
+    for (uint64_t i = 0; i < n; i++) mbytes += pad ? pad : k[i % kSelfTestCases].mlen;
+    const uint64_t o_off = 96 * n, o_msg = o_off + 8 * (n + 1), o_acc = (o_msg + mbytes + 64 + 15) / 16 * 16,
+                   o_dig = (o_acc + n + 15) / 16 * 16, total = o_dig + 32 * n;
+    if (pin) {
+      void* p = nullptr;
+      if (hipHostMalloc(&p, total, hipHostMallocPortable) != hipSuccess) return set_err(EDV_E_OOM, "hipHostMalloc");
+      base = static_cast<uint8_t*>(p);
+      memset(base, 0, total);
+    }
+    try {  // the C-ABI never throws
+      if (!pin) heap.assign(total, 0);
+      want.resize(n);
+    } catch (const std::bad_alloc&) {
+      return set_err(EDV_E_OOM, "host memory for a self-test batch");
+    }
+    if (!pin) base = heap.data();
+    sigs = base;
+    pks = base + 64 * n;
+    off = reinterpret_cast<uint64_t*>(base + o_off);
+    msgs = base + o_msg;
+    accept = base + o_acc;
+    digests = base + o_dig;
+    uint64_t pos = 0;
+    for (uint64_t i = 0; i < n; i++) {
+      const SelfTestCase& t = k[i % kSelfTestCases];
+      memcpy(sigs + 64 * i, t.sig, 64);
+      memcpy(pks + 32 * i, t.pk, 32);
+      off[i] = pos;
+      if (!pad) memcpy(msgs + pos, t.msg, t.mlen);
+      pos += pad ? pad : t.mlen;
+      want[i] = t.accept;
+    }
+    off[n] = pos;
+    return 0;
+  }
+  ~KatBatch() {
+    if (pinned && base) (void)hipHostFree(base);
+  }
+};
+
+// One family of edv_self_test: the case list tiled to the smallest batch that
+// routes to the family's kernels, through the synchronous path, every verdict
+// compared with libsodium's.  Caller holds c.mu.
+int selftest_family(DevCtx& c, uint32_t family) {
+  const char* name = family == EDV_SELFTEST_RTL ? "RTL" : family == EDV_SELFTEST_TWO_WALK ? "TWO_WALK" : "BATCH";
+  const uint64_t n = family == EDV_SELFTEST_RTL ? 16 : family == EDV_SELFTEST_TWO_WALK ? kRtlMax + 1 : 256;
+  KatBatch b;
+  int err;
+  if ((err = b.build(n, 0, false))) return err;
+  // the latency kernels whatever the device's latency-path limit is (n picks
+  // the kernel), or the batch kernels with that limit bypassed for this call
+  err = family == EDV_SELFTEST_BATCH ? run_shard(c, b.sigs, b.pks, b.msgs, b.off, 0, n, b.accept, -1, true)
+                                     : run_shard_quad(c, b.sigs, b.pks, b.msgs, b.off, 0, n, b.accept);
+  if (err) {
+    quiesce(c);
+    return err;
+  }
+  for (uint64_t i = 0; i < n; i++) {
+    if (b.accept[i] == b.want[i]) continue;
+    char buf[160];
+    snprintf(buf, sizeof buf, "self-test failed: family %s, case %d (request %llu of %llu): verdict %d, libsodium's %d",
+             name, int(i % kSelfTestCases), (unsigned long long)i, (unsigned long long)n, int(b.accept[i]),
+             int(b.want[i]));
+    return set_err(EDV_E_SELFTEST, buf);
+  }
+  return 0;
+}
+int run_selftest(DevCtx& c, uint32_t families) {
+  int err;
+  for (uint32_t f : {uint32_t(EDV_SELFTEST_RTL), uint32_t(EDV_SELFTEST_TWO_WALK), uint32_t(EDV_SELFTEST_BATCH)})
+    if ((families & f) && (err = selftest_family(c, f))) return err;
+  return 0;
+}
+
+// One warm-up batch of n requests through the synchronous path, and through
+// every asynchronous slot if asked (with digests, as a Node's prod asks for
+// them), so that the buffers and table sets such a batch needs exist.
+int warm_up(DevCtx& c, uint64_t n, bool async, bool pin) {
+  KatBatch b;
+  int err;
+  if ((err = b.build(n, kPrepareMsgBytes, pin))) return err;
+  if ((err = run_shard(c, b.sigs, b.pks, b.msgs, b.off, 0, n, b.accept, 1))) {
+    quiesce(c);
+    return err;
+  }
+  for (int k = 0; async && k < kAsyncSlots; k++) {
+    int64_t t = -1;
+    DevCtx::AsyncSlot& s = c.as[c.ledger.next % kAsyncSlots];
+    if ((err = submit_async(c, b.sigs, b.pks, b.msgs, b.off, n, b.accept, b.digests, true, &t))) {
+      quiesce(c);
+      for (auto& a : c.as)
+        if (a.st) (void)hipStreamSynchronize(a.st);
+      (void)hipGetLastError();
+      return err;
+    }
+    if ((err = async_complete(c, s))) return err;
+  }
+  return 0;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------ C-ABI
@@ -1901,6 +2222,106 @@ int edv_set_length_buckets(int device, int mode) {
 }
 
 
+int edv_set_table_policy(int device, int policy) {
+  g_err.clear();
+  if (policy != EDV_TABLES_AUTO && policy != EDV_TABLES_COMPACT && policy != EDV_TABLES_LARGE)
+    return set_err(EDV_E_ARG, "table policy must be EDV_TABLES_AUTO, _COMPACT or _LARGE");
+  int err = 0;
+  DevCtx* c = get_ctx(device, &err);
+  if (!c) return err;
+  std::lock_guard<std::mutex> lk(c->mu);
+  c->policy = policy;  // the next batch builds what it asks for (pick_tables); nothing is freed here
+  c->sb_failed = false;
+  return 0;
+}
+
+int edv_table_state(int device, uint64_t out[4]) {
+  g_err.clear();
+  if (!out) return set_err(EDV_E_ARG, "null pointer");
+  for (int k = 0; k < 4; k++) out[k] = 0;
+  int err = 0;
+  DevCtx* c = get_ctx(device, &err);
+  if (!c) return err;
+  std::lock_guard<std::mutex> lk(c->mu);
+  out[0] = uint64_t(c->policy);
+  out[1] = c->sb_compact ? sb_alloc_bytes(sb_compact()) : 0;
+  out[2] = c->sb_large ? sb_alloc_bytes(sb_large()) : 0;
+  out[3] = c->sb_failed ? 1 : 0;
+  return 0;
+}
+
+int edv_self_test(int device, uint32_t families) {
+  g_err.clear();
+  const uint32_t all = EDV_SELFTEST_RTL | EDV_SELFTEST_TWO_WALK | EDV_SELFTEST_BATCH;
+  if (families == 0 || (families & ~all)) return set_err(EDV_E_ARG, "self-test families: a mask of EDV_SELFTEST_*");
+  CtxLock cl(device);
+  if (cl.err) return cl.err;
+  return run_selftest(*cl.c, families);
+}
+
+int edv_prepare(int device, uint64_t max_batch, uint32_t flags) {
+  g_err.clear();
+  if (max_batch == 0 || max_batch > kPrepareMax || (flags & ~uint32_t(EDV_PREPARE_ASYNC)))
+    return set_err(EDV_E_ARG, "prepare: 0 < max_batch <= 2^20, flags 0 or EDV_PREPARE_ASYNC");
+  CtxLock cl(device);
+  if (cl.err) return cl.err;
+  DevCtx& c = *cl.c;
+  const bool was_failed = c.sb_failed;
+  // one warm-up batch per route a batch of at most max_batch can take: the
+  // right-to-left kernel, the two-walk kernel, the batch kernels
+  std::vector<uint64_t> sizes = {max_batch < kRtlMax ? max_batch : kRtlMax, max_batch};
+  if (c.quad_max) sizes.push_back(max_batch < c.quad_max ? max_batch : c.quad_max);
+  std::sort(sizes.begin(), sizes.end());
+  sizes.erase(std::unique(sizes.begin(), sizes.end()), sizes.end());
+  int err;
+  for (const uint64_t n : sizes)
+    for (const bool pin : {false, true})
+      if ((err = warm_up(c, n, (flags & EDV_PREPARE_ASYNC) != 0, pin))) return err;
+  // a build of the large set that failed here: the batches would run (on the
+  // compact set), but a Node had better know at start-up
+  if (c.sb_failed && !was_failed) return c.sb_err ? c.sb_err : EDV_E_OOM;
+  uint32_t families = EDV_SELFTEST_RTL;
+  if (max_batch > kRtlMax) families |= EDV_SELFTEST_TWO_WALK;
+  if (max_batch > c.quad_max) families |= EDV_SELFTEST_TWO_WALK | EDV_SELFTEST_BATCH;
+  return run_selftest(c, families);
+}
+
+int edv_trim(int device, uint64_t keep_batch) {
+  g_err.clear();
+  int err = 0;
+  DevCtx* c = get_ctx(device, &err);
+  if (!c) return err;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!c->ready) {
+    c->sb_failed = false;
+    return 0;
+  }
+  if (ctx_busy(*c)) return set_err(EDV_E_BUSY, "trim: asynchronous or pipelined batches not yet handed over");
+  HIPOK(hipSetDevice(c->phys), "hipSetDevice");
+  if ((err = drain(*c))) return err;
+  c->sb_failed = false;
+  trim_buffers(*c, keep_batch);
+  trim_tables(*c, keep_batch, false);
+  return 0;
+}
+
+int edv_release(int device) {
+  g_err.clear();
+  int err = 0;
+  DevCtx* c = get_ctx(device, &err);
+  if (!c) return err;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!c->ready) {
+    c->sb_failed = false;
+    return 0;
+  }
+  if (ctx_busy(*c)) return set_err(EDV_E_BUSY, "release: asynchronous or pipelined batches not yet handed over");
+  HIPOK(hipSetDevice(c->phys), "hipSetDevice");
+  if ((err = drain(*c))) return err;
+  c->sb_failed = false;
+  ctx_destroy(*c);
+  return 0;
+}
 
 int edv_dev_alloc(int device, uint64_t bytes, void** out) {
   int phys, err;

@@ -33,6 +33,12 @@ EDV_E_ARG = -1
 EDV_E_NODEV = -2
 EDV_E_HIP = -3
 EDV_E_OOM = -4
+EDV_E_BUSY = -5      # trim / release: batches not yet handed over still own caller buffers
+EDV_E_SELFTEST = -6  # self_test / prepare: a verdict differs from libsodium's
+TABLES_AUTO, TABLES_COMPACT, TABLES_LARGE = 0, 1, 2   # set_table_policy
+SELFTEST_RTL, SELFTEST_TWO_WALK, SELFTEST_BATCH = 1, 2, 4
+SELFTEST_ALL = 7
+PREPARE_ASYNC = 1
 FLAG_UNIFORM_LENGTH = 1  # every message has the same SHA-512 block count: no length buckets
 FLAG_BUCKETS = 2         # always bucket by SHA-512 block count
 FLAG_SPLIT_PREP = 4      # pipelined path: batch k+1's hash side beside batch k's main kernel
@@ -128,6 +134,18 @@ def lib():
         h.edv_pack_bits_dev.restype = ctypes.c_int
         h.edv_context_memory.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
         h.edv_context_memory.restype = ctypes.c_int
+        h.edv_set_table_policy.argtypes = [ctypes.c_int, ctypes.c_int]
+        h.edv_set_table_policy.restype = ctypes.c_int
+        h.edv_table_state.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
+        h.edv_table_state.restype = ctypes.c_int
+        h.edv_self_test.argtypes = [ctypes.c_int, ctypes.c_uint32]
+        h.edv_self_test.restype = ctypes.c_int
+        h.edv_prepare.argtypes = [ctypes.c_int, u64, ctypes.c_uint32]
+        h.edv_prepare.restype = ctypes.c_int
+        h.edv_trim.argtypes = [ctypes.c_int, u64]
+        h.edv_trim.restype = ctypes.c_int
+        h.edv_release.argtypes = [ctypes.c_int]
+        h.edv_release.restype = ctypes.c_int
         h.edv_dev_alloc.argtypes = [ctypes.c_int, u64, ctypes.POINTER(ctypes.c_void_p)]
         h.edv_dev_free.argtypes = [ctypes.c_int, vp]
         h.edv_h2d.argtypes = [ctypes.c_int, vp, vp, u64]
@@ -201,6 +219,50 @@ def context_memory(device: int = 0) -> dict:
     out = (ctypes.c_uint64 * 7)()
     _check(lib().edv_context_memory(device, out))
     return dict(zip(CONTEXT_MEMORY_FIELDS, (int(x) for x in out)))
+
+
+TABLE_STATE_FIELDS = ("policy", "compact_bytes", "large_bytes", "large_failed")
+
+
+def set_table_policy(device: int, policy: int):
+    """Which [S]B table set the next batches of `device` use: TABLES_AUTO,
+    TABLES_COMPACT or TABLES_LARGE (edv_set_table_policy).  Never changes verdicts."""
+    _check(lib().edv_set_table_policy(device, policy))
+
+
+def table_state(device: int = 0) -> dict:
+    """The table policy of `device`, the bytes of the compact and of the large
+    set its context holds, and whether a build of the large set has failed and
+    is not being retried (edv_table_state)."""
+    out = (ctypes.c_uint64 * 4)()
+    _check(lib().edv_table_state(device, out))
+    return dict(zip(TABLE_STATE_FIELDS, (int(x) for x in out)))
+
+
+def self_test(device: int = 0, families: int = SELFTEST_ALL):
+    """Known-answer test of the kernel families in `families` (SELFTEST_*) on
+    `device`; raises EdvError(EDV_E_SELFTEST) if a verdict is not libsodium's."""
+    _check(lib().edv_self_test(device, families))
+
+
+def prepare(device: int = 0, max_batch: int = 400, flags: int = 0):
+    """Create the context of `device`, build and grow what batches of up to
+    max_batch requests need (flags: PREPARE_ASYNC for the asynchronous slots
+    too) and self-test the kernels they take (edv_prepare)."""
+    _check(lib().edv_prepare(device, max_batch, flags))
+
+
+def trim(device: int = 0, keep_batch: int = 0):
+    """Free what is larger than a batch of keep_batch needs and the table sets
+    the policy would not pick for it; EdvError(EDV_E_BUSY) while asynchronous
+    batches are not handed over (edv_trim)."""
+    _check(lib().edv_trim(device, keep_batch))
+
+
+def release(device: int = 0):
+    """Destroy the context of `device`; its settings stay, the next call makes
+    a fresh one; EdvError(EDV_E_BUSY) as for trim (edv_release)."""
+    _check(lib().edv_release(device))
 
 
 def device_count() -> int:

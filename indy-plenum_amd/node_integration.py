@@ -128,6 +128,31 @@ class PendingProd:
             on_client(msg, frm, _as_outcome(next(it)))
 
 
+def prepare_node(max_prod: int = 4 * DEFAULT_LISTENER_QUOTA, device: Optional[int] = None, compact_only: bool = True,
+                 async_slots: bool = True) -> dict:
+    """The recommended start-up step of a Node, before it reads its first
+    client message: everything the first prod's batch would otherwise pay for
+    inside its verify (the HIP runtime, the context's streams, the [S]B table
+    set, scratch and pinned staging: ~0.1 s against ~0.4 ms warm) happens here,
+    and the kernels are checked against known libsodium answers on this GPU
+    (edv_prepare).  max_prod: the most requests one prod authenticates (client
+    REQUESTs plus PROPAGATEs of one listener read each, DEFAULT_LISTENER_QUOTA).
+    compact_only: pin the device to the 64 MiB table set, so that no batch,
+    however large, makes this process build and keep the 3 GiB one
+    (edv.TABLES_COMPACT).  async_slots: also grow the slots PendingProd's
+    submissions take.  device None: the device edv.batch_device() gives the
+    native path.  Returns {"device", "tables": edv.table_state, "memory":
+    edv.context_memory}.  Raises EdvUnavailable without a GPU and EdvError
+    (EDV_E_SELFTEST) if a verdict is wrong: a Node must not start then."""
+    from . import edv
+    if device is None:
+        device = edv.batch_device()
+    if compact_only:
+        edv.set_table_policy(device, edv.TABLES_COMPACT)
+    edv.prepare(device, max_prod, edv.PREPARE_ASYNC if async_slots else 0)
+    return {"device": device, "tables": edv.table_state(device), "memory": edv.context_memory(device)}
+
+
 def _as_outcome(r):
     """authenticate_batch's per-request result: the identifier set, or the
     exception instance verifySignature would raise."""
@@ -145,4 +170,5 @@ def failed(outcome) -> Optional[BaseException]:
     return outcome if isinstance(outcome, BaseException) else None
 
 
-__all__: List[str] = ["DEFAULT_LISTENER_QUOTA", "PendingProd", "ProdAuthBatch", "authenticate_prod", "failed"]
+__all__: List[str] = ["DEFAULT_LISTENER_QUOTA", "PendingProd", "ProdAuthBatch", "authenticate_prod", "failed",
+                      "prepare_node"]
