@@ -156,7 +156,14 @@ int edv_verify_batch_dev_flags(const uint8_t *d_sigs, const uint8_t *d_pks, cons
  */
 int edv_sha256_batch(const uint8_t *msgs, const uint64_t *msg_off, uint64_t n, uint8_t *out, uint32_t device_mask);
 /* Device-resident form, async on `stream` (NULL = library stream, synchronised);
- * d_msgs readable 8 bytes past the last message byte; d_out n x 32 bytes. */
+ * d_msgs readable 8 bytes past the last message byte; d_out n x 32 bytes.
+ * Offsets are absolute into d_msgs minus msg_base, as for edv_verify_batch_dev.
+ * EDV_E_ARG, with nothing launched: d_msg_off not 8-byte or d_out not 16-byte
+ * aligned (the offsets are read as 64-bit words, each digest is stored as two
+ * 16-byte vectors; d_msgs may have any alignment), or n > 0 with d_msgs,
+ * d_msg_off or d_out NULL.  A NULL d_msgs is refused whenever n > 0, even if
+ * every message is empty: the offsets live in device memory, so the library
+ * cannot know that without reading them. */
 int edv_sha256_batch_dev(const uint8_t *d_msgs, const uint64_t *d_msg_off, uint64_t msg_base, uint64_t n,
                          uint8_t *d_out, int device, void *stream);
 

@@ -95,6 +95,15 @@ int edv_test_fail_async(int device, int64_t ticket);
  *   EUCLID_DIV              r0, t0, r1, t1 (128)        r0, t0 (64)
  *   GE_FROMBYTES            32 bytes                    words ge_is_canonical, has_small_order,
  *                                                       ge_frombytes_negate, then X Y Z T limbs (172)
+ * The batch signer's arithmetic (sign_one, edv_verify_core.h):
+ *   SC_MULADD               a, b, c scalars (96)        (a b + c) mod L (32)
+ *   RECODE8                 scalar < 2^253 (32)         the 32 packed signed radix-256 digits (32)
+ *   SCALARMULT_BASE         k < 2^253 (32)              scalarmult_base's X Y Z T limbs (160), then
+ *                                                       ge_p3_tobytes of that point (32): 192.  Walks the
+ *                                                       context's own comb table (built on first use, as
+ *                                                       edv_sign_batch_dev builds it) through the sign
+ *                                                       kernel's GlobalComb view
+ *   GE_P3_TOBYTES           X Y Z T limbs (160)         32 bytes
  * One quad (4 consecutive lanes, coordinate q on lane q) per case:
  *   QUAD_SQ_SHIFT           4 x (limbs, sh word) (176)  4 x limbs (160)
  *   QUAD_DBL                4 x limbs (160)             4 x limbs (160)
@@ -122,6 +131,10 @@ int edv_test_fail_async(int device, int64_t ticket);
 #define EDV_PROBE_QUAD_ADD 18
 #define EDV_PROBE_QUAD_CACHED 19
 #define EDV_PROBE_QUAD_CACHED_SIGNED 20
+#define EDV_PROBE_SC_MULADD 21
+#define EDV_PROBE_RECODE8 22
+#define EDV_PROBE_SCALARMULT_BASE 23
+#define EDV_PROBE_GE_P3_TOBYTES 24
 int edv_probe_math(int device, int op, const void *in, uint64_t in_stride, void *out, uint64_t out_stride, uint64_t n);
 
 /*

@@ -211,7 +211,11 @@ int hc_probe_math(int op, const void* in, uint64_t in_stride, void* out, uint64_
       HC_PROBE_CASE(EDV_PROBE_FDIV_FLOOR)
       HC_PROBE_CASE(EDV_PROBE_EUCLID_DIV)
       HC_PROBE_CASE(EDV_PROBE_GE_FROMBYTES)
+      HC_PROBE_CASE(EDV_PROBE_SC_MULADD)
+      HC_PROBE_CASE(EDV_PROBE_RECODE8)
+      HC_PROBE_CASE(EDV_PROBE_GE_P3_TOBYTES)
 #undef HC_PROBE_CASE
+      case EDV_PROBE_SCALARMULT_BASE: probe_scalarmult_base(x, y, comb()); break;
       default: return -1;
     }
   }

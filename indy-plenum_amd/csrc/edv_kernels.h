@@ -1,7 +1,8 @@
 // edv_kernels.h -- what the prep kernel (edv_prep.hip) and the main kernel and
 // host runtime (edv_verify.hip) share: the per-chunk state layout, the kernel
-// arguments, the per-signature table view used by the prep kernel, and the
-// prep launch entry point.  Two translation units so the prep kernel is built
+// arguments, the per-signature table view used by the prep kernel, the batch
+// signer's view of its comb table (the sign kernel's, and the tests' probe
+// kernel's in libedv_measure.so), and the prep launch entry point.  Two translation units so the prep kernel is built
 // without the scheduling fences of the field arithmetic (edv_math.h
 // sched_fence): they keep the main kernel's registers in check, while the
 // prep kernel's serial exponentiations and table chain run faster when LLVM
@@ -91,6 +92,21 @@ __device__ __forceinline__ void load_words(uint32_t* out, const uint32_t* p, int
     out[4 * k] = v.x; out[4 * k + 1] = v.y; out[4 * k + 2] = v.z; out[4 * k + 3] = v.w;
   }
 }
+
+// Comb rows for the batch signer, in global memory (528 KB, L2-resident).
+struct GlobalComb {
+  const int32_t* w;
+  __device__ __forceinline__ ge_precomp entry(int i, int j) const {
+    const int4* p = reinterpret_cast<const int4*>(w + (i * kCombEntries + j) * kBStride);
+    int32_t t[32];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      const int4 v = p[k];
+      t[4 * k] = v.x; t[4 * k + 1] = v.y; t[4 * k + 2] = v.z; t[4 * k + 3] = v.w;
+    }
+    return precomp_from_words(t);
+  }
+};
 
 namespace {  // per translation unit (the prep kernel's codegen depends on it: +368 B of scratch otherwise)
 // The R side's view of the [S]B tables: stage() copies the lane's entry

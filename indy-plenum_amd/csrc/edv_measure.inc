@@ -218,11 +218,14 @@ int edv_probe_math(int device, int op, const void* in, uint64_t in_stride, void*
     }
   } din, dout;
   if (din.ensure(n * in_stride) || dout.ensure(n * out_stride)) return EDV_E_OOM;
+  int err;
+  if (op == EDV_PROBE_SCALARMULT_BASE && (err = ensure_comb(*c))) return err;  // the signer's table, as it builds it
   HIPOK(hipMemcpyAsync(din.p, in, n * in_stride, hipMemcpyHostToDevice, c->stream), "probe copy in");
   HIPOK(hipMemsetAsync(dout.p, 0, n * out_stride, c->stream), "probe memset");
-  HIPOK((probe_is_quad(op) ? launch_probe_quad : launch_probe_lane)(c->stream, op, static_cast<const uint8_t*>(din.p),
-                                                                    in_stride, static_cast<uint8_t*>(dout.p),
-                                                                    out_stride, n),
+  HIPOK(probe_is_quad(op) ? launch_probe_quad(c->stream, op, static_cast<const uint8_t*>(din.p), in_stride,
+                                              static_cast<uint8_t*>(dout.p), out_stride, n)
+                          : launch_probe_lane(c->stream, op, static_cast<const uint8_t*>(din.p), in_stride,
+                                              static_cast<uint8_t*>(dout.p), out_stride, n, c->comb),
         "probe launch");
   HIPOK(hipMemcpyAsync(out, dout.p, n * out_stride, hipMemcpyDeviceToHost, c->stream), "probe copy out");
   HIPOK(hipStreamSynchronize(c->stream), "probe sync");  // the buffers are freed on return

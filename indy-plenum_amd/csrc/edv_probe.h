@@ -2,7 +2,8 @@
 // edv_probe_quad.hip: libedv_measure.so only), for edv_measure.inc.  Device
 // buffers, strides in bytes (multiples of 4, at least probe_size(op)); each
 // launches on stream s and returns hipGetLastError(), hipErrorInvalidValue for
-// an op that is not its kind.
+// an op that is not its kind.  comb: the context's comb table (the batch
+// signer's, edv_launch.h), read by EDV_PROBE_SCALARMULT_BASE only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -12,7 +13,7 @@
 namespace edv {
 
 hipError_t launch_probe_lane(hipStream_t s, int op, const uint8_t* in, uint64_t in_stride, uint8_t* out,
-                             uint64_t out_stride, uint64_t n);
+                             uint64_t out_stride, uint64_t n, const int32_t* comb);
 hipError_t launch_probe_quad(hipStream_t s, int op, const uint8_t* in, uint64_t in_stride, uint8_t* out,
                              uint64_t out_stride, uint64_t n);
 

@@ -35,6 +35,10 @@ EDV_HD constexpr ProbeSize probe_size(int op) {
     case EDV_PROBE_QUAD_CACHED: return ProbeSize{160, 160};
     case EDV_PROBE_QUAD_ADD: return ProbeSize{320, 160};
     case EDV_PROBE_QUAD_CACHED_SIGNED: return ProbeSize{164, 160};
+    case EDV_PROBE_SC_MULADD: return ProbeSize{96, 32};
+    case EDV_PROBE_RECODE8: return ProbeSize{32, 32};
+    case EDV_PROBE_SCALARMULT_BASE: return ProbeSize{32, 192};
+    case EDV_PROBE_GE_P3_TOBYTES: return ProbeSize{160, 32};
     default: return ProbeSize{0, 0};
   }
 }
@@ -49,6 +53,13 @@ EDV_HD fe probe_fe(const uint32_t* x) {
 EDV_HD void probe_put(uint32_t* y, const fe& f) {
 #pragma unroll
   for (int i = 0; i < 10; i++) y[i] = uint32_t(f.v[i]);
+}
+EDV_HD ge_p3 probe_p3(const uint32_t* x) { return ge_p3{probe_fe(x), probe_fe(x + 10), probe_fe(x + 20), probe_fe(x + 30)}; }
+EDV_HD void probe_put_p3(uint32_t* y, const ge_p3& p) {
+  probe_put(y, p.X);
+  probe_put(y + 10, p.Y);
+  probe_put(y + 20, p.Z);
+  probe_put(y + 30, p.T);
 }
 EDV_HD double probe_f64(const uint32_t* x) { return __builtin_bit_cast(double, pack64(x[0], x[1])); }
 EDV_HD void probe_put_f64(uint32_t* y, double d) {
@@ -117,8 +128,7 @@ EDV_HD void probe_lane_op(const uint32_t* x, uint32_t* y) {
     euclid_div(r0, t0, r1, t1);
 #pragma unroll
     for (int i = 0; i < 8; i++) { y[i] = r0[i]; y[8 + i] = t0[i]; }
-  } else {
-    static_assert(OP == EDV_PROBE_GE_FROMBYTES, "a one-lane probe op");
+  } else if constexpr (OP == EDV_PROBE_GE_FROMBYTES) {
     uint32_t s[8];
 #pragma unroll
     for (int i = 0; i < 8; i++) s[i] = x[i];
@@ -126,11 +136,43 @@ EDV_HD void probe_lane_op(const uint32_t* x, uint32_t* y) {
     y[0] = ge_is_canonical(s) ? 1u : 0u;
     y[1] = has_small_order(s) ? 1u : 0u;
     y[2] = ge_frombytes_negate(p, s) ? 1u : 0u;
-    probe_put(y + 3, p.X);
-    probe_put(y + 13, p.Y);
-    probe_put(y + 23, p.Z);
-    probe_put(y + 33, p.T);
+    probe_put_p3(y + 3, p);
+  } else if constexpr (OP == EDV_PROBE_SC_MULADD) {
+    uint32_t a[8], b[8], c[8], o[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) { a[i] = x[i]; b[i] = x[8 + i]; c[i] = x[16 + i]; }
+    sc_muladd(o, a, b, c);
+#pragma unroll
+    for (int i = 0; i < 8; i++) y[i] = o[i];
+  } else if constexpr (OP == EDV_PROBE_RECODE8) {
+    uint32_t s[8], d[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) s[i] = x[i];
+    recode8(d, s);
+#pragma unroll
+    for (int i = 0; i < 8; i++) y[i] = d[i];
+  } else {
+    static_assert(OP == EDV_PROBE_GE_P3_TOBYTES, "a one-lane probe op");
+    uint32_t w[8];
+    ge_p3_tobytes(w, probe_p3(x));
+#pragma unroll
+    for (int i = 0; i < 8; i++) y[i] = w[i];
   }
+}
+
+// EDV_PROBE_SCALARMULT_BASE: the signer's comb walk over the caller's table
+// view (GlobalComb on the device, HostComb on the CPU), the point as it comes
+// out and its encoding
+template <class CombTab>
+EDV_HD void probe_scalarmult_base(const uint32_t* x, uint32_t* y, const CombTab& ct) {
+  uint32_t k[8], w[8];
+#pragma unroll
+  for (int i = 0; i < 8; i++) k[i] = x[i];
+  const ge_p3 p = scalarmult_base(k, ct);
+  probe_put_p3(y, p);
+  ge_p3_tobytes(w, p);
+#pragma unroll
+  for (int i = 0; i < 8; i++) y[40 + i] = w[i];
 }
 
 }  // namespace edv

@@ -2070,6 +2070,11 @@ int edv_pack_bits_dev(const uint8_t* d_accept, uint64_t n, uint8_t* d_bits, int 
 int edv_sha256_batch_dev(const uint8_t* d_msgs, const uint64_t* d_msg_off, uint64_t msg_base, uint64_t n,
                          uint8_t* d_out, int device, void* stream) {
   g_err.clear();
+  // before anything reaches the GPU: the kernel reads the offsets as 64-bit
+  // words and stores each digest as two 16-byte vectors
+  if (n && (!d_msgs || !d_msg_off || !d_out)) return set_err(EDV_E_ARG, "sha256: null d_msgs / d_msg_off / d_out");
+  if ((reinterpret_cast<uintptr_t>(d_msg_off) & 7) || (reinterpret_cast<uintptr_t>(d_out) & 15))
+    return set_err(EDV_E_ARG, "sha256: d_msg_off must be 8-byte and d_out 16-byte aligned");
   CtxLock cl(device);
   if (cl.err) return cl.err;
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : cl.c->stream;

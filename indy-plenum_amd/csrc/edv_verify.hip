@@ -125,21 +125,6 @@ __global__ __launch_bounds__(kBlock) void edv_main_kernel_prio(VerifyArgs a) {
   EDV_MAIN_BODY
 }
 
-// Comb rows for the batch signer, in global memory (528 KB, L2-resident).
-struct GlobalComb {
-  const int32_t* w;
-  __device__ __forceinline__ ge_precomp entry(int i, int j) const {
-    const int4* p = reinterpret_cast<const int4*>(w + (i * kCombEntries + j) * kBStride);
-    int32_t t[32];
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-      const int4 v = p[k];
-      t[4 * k] = v.x; t[4 * k + 1] = v.y; t[4 * k + 2] = v.z; t[4 * k + 3] = v.w;
-    }
-    return precomp_from_words(t);
-  }
-};
-
 // Batch signer (row f-4: synthetic load generation): seeds -> (pk, sig) over M.
 __global__ __launch_bounds__(kBlock) void edv_sign_kernel(const uint32_t* seeds, const uint8_t* msgs,
                                                           const uint64_t* off, uint64_t msg_base, uint64_t n,

@@ -380,6 +380,20 @@ def verify_async(sigs: np.ndarray, pks: np.ndarray, msgs: np.ndarray, offsets: n
     return t.value
 
 
+def verify_digest_async(sigs, pks, msgs, offsets, n: int, accept, digests=None, device: int = 0) -> int:
+    """Queue one host batch with its SHA-256 digests (edv_verify_digest_batch_async)
+    and return its ticket.  Every buffer is a numpy array or a raw address (a
+    PinnedBuffer's .ptr plus an offset); digests None passes NULL.  No size
+    checks: the caller owns the layout, and the buffers until wait_async."""
+    def addr(a):
+        return a.ctypes.data if isinstance(a, np.ndarray) else a
+    t = ctypes.c_int64(-1)
+    _check(lib().edv_verify_digest_batch_async(addr(sigs), addr(pks), addr(msgs), addr(offsets), n, addr(accept),
+                                               None if digests is None else addr(digests), device,
+                                               ctypes.byref(t)))
+    return t.value
+
+
 def wait_async(ticket: int, device: int = 0) -> None:
     """Wait until batch `ticket` has its verdicts in its accept array."""
     _check(lib().edv_wait_async(device, ticket))
@@ -701,6 +715,8 @@ PROBE_OPS = {
     "approx_div": (12, 16, 8), "fdiv_floor": (13, 16, 8), "euclid_div": (14, 128, 64),
     "ge_frombytes": (15, 32, 172), "quad_sq_shift": (16, 176, 160), "quad_dbl": (17, 160, 160),
     "quad_add": (18, 320, 160), "quad_cached": (19, 160, 160), "quad_cached_signed": (20, 164, 160),
+    "sc_muladd": (21, 96, 32), "recode8": (22, 32, 32), "scalarmult_base": (23, 32, 192),
+    "ge_p3_tobytes": (24, 160, 32),
 }
 
 

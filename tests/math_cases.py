@@ -19,6 +19,7 @@ identity entry (1 | 1 | 0 | 1).  quad_cached multiplies by fe_one() and
 fe_d2(), whose limbs are below RED.  So the extremes the callers can reach
 are +-RED in every sign pattern; quad_bounds() pushes that bound through the
 two stages of quad_dbl and quad_add as written."""
+import functools
 import random
 from fractions import Fraction
 
@@ -766,3 +767,182 @@ def family_quad_points(run, base_points):
     got = pl.unpack_limbs(run("quad_add", pl.pack_limbs([a + b for a, b in zip(ext_p, cneg)])))
     for (a, b), g in zip(pairs, got):
         assert affine(g) == ed_add(a, ((P - b[0]) % P, b[1])), ("quad_add of -Q", a, b)
+
+
+# ------------------------------------------------------- the signer's arithmetic
+# sign_one (edv_verify_core.h) is sc_muladd, two scalarmult_base walks over the
+# comb table (recode8 digits, ge_precomp_cneg) and ge_p3_tobytes.
+SC_EDGES = [0, 1, 2, L - 1, L, L + 1, 2**252, 2**255 - 8, M256]     # 2^255 - 8: the largest clamped scalar
+
+
+def sc_muladd_cases():
+    """(a, b, c) below 2^256: every triple over SC_EDGES; all words 0xffffffff
+    (the largest column sum: the 96-bit accumulator's top word at its maximum,
+    and the carry above 2^32 that must survive into the next column); a = 2^(32
+    i) - 1, b = 2^(32 j) - 1 with c = 0 and c = 2^256 - 1 (the carries of one
+    column at a time); a b + c = 0 (mod L) by construction; 2,000 random
+    triples; the signer's shape (h < L, a clamped, r < L)"""
+    r = random.Random(91)
+    cases = [(a, b, c) for a in SC_EDGES for b in SC_EDGES for c in SC_EDGES]
+    cases.append((M256, M256, M256))
+    cases += [(2**(32 * i) - 1, 2**(32 * j) - 1, c) for i in range(1, 9) for j in range(1, 9) for c in (0, M256)]
+    for _ in range(100):
+        a, b = r.randrange(2**256), r.randrange(2**256)
+        c = -a * b % L
+        cases += [(a, b, c), (a, b, c + L * r.randrange(1, 15))]
+    cases += [(0, r.randrange(2**256), 0), (L, r.randrange(2**256), L), (r.randrange(2**256), 8 * L, 15 * L)]
+    cases += [(r.randrange(2**256), r.randrange(2**256), r.randrange(2**256)) for _ in range(2000)]
+    for _ in range(300):
+        clamped = (r.randrange(2**256) & (2**255 - 8) & ~(1 << 255)) | (1 << 254)
+        cases.append((r.randrange(L), clamped, r.randrange(L)))
+    assert all(0 <= v < 2**256 for t in cases for v in t)
+    return cases
+
+
+def family_sc_muladd(run):
+    """sc_muladd: out == (a b + c) mod L and out < L.  -> the number of cases"""
+    cases = sc_muladd_cases()
+    out = pl.unpack_ints(run("sc_muladd", pl.pack_ints(cases, 32)), 32)
+    assert len(out) == len(cases)
+    for (a, b, c), o in zip(cases, out):
+        assert o[0] < L and o[0] == (a * b + c) % L, ("sc_muladd", hex(a), hex(b), hex(c), hex(o[0]))
+    return len(cases)
+
+
+def py_recode8(k):
+    """the unique digits d_i in [-128, 127] (i < 31), d_31 >= 0, with sum d_i 256^i == k"""
+    out = []
+    for _ in range(31):
+        d = k & 255
+        if d >= 128:
+            d -= 256
+        out.append(d)
+        k = (k - d) >> 8
+    return out + [k]
+
+
+def recode8_values():
+    """scalars below 2^253: the CPU tests' recoding values; 0x7f and 0x80 alone
+    in every byte position; 0x80 repeated (a carry through all 31 lower digits);
+    0x7f...7f80; 0xff... ; 2^253 - 1"""
+    vals = recoding_values()
+    vals += [b << (8 * i) for i in range(32) for b in (0x7f, 0x80)]
+    vals += [int("80" * 31, 16), int("80" * 31, 16) | 0x10 << 248, int("7f" * 30 + "80", 16),
+             int("1f" + "7f" * 30 + "80", 16), int("ff" * 31, 16), int("1f" + "ff" * 31, 16), 2**253 - 1, 2**253 - 2**248]
+    return [v for v in vals if 0 <= v < 2**253]
+
+
+def family_recode8(run):
+    """recode8: every digit in [-128, 127], the top one >= 0, sum d_i 256^i == s.  -> the number of cases"""
+    vals = recode8_values()
+    out = np.ascontiguousarray(run("recode8", pl.pack_ints([[v] for v in vals], 32))).view(np.uint32).tolist()
+    for v, o in zip(vals, out):
+        d = signed_digits(o, 8)
+        assert len(d) == 32 and all(-128 <= x <= 127 for x in d) and d[31] >= 0, hex(v)
+        assert sum(x << (8 * i) for i, x in enumerate(d)) == v, hex(v)
+        assert d == py_recode8(v), hex(v)
+    return len(vals)
+
+
+def scalarmult_base_digit_cases():
+    """Signed radix-256 digit vectors (top digit >= 0, value in [0, 2^253)), so
+    the walk's table index and sign are chosen per row: for each row one
+    non-zero digit of +1, +127 (row 31: +31, the largest below 2^253), -1, -127
+    and -128 (a negative one under +1 in the next row, and in row 31); every
+    digit -128 under a top digit of 1; every digit +127; alternating neighbours
+    at the two extremes"""
+    cases = []
+    for i in range(32):
+        for d in (1, 127, -1, -127, -128):
+            if d > 0:
+                v = [0] * 32
+                v[i] = d if i < 31 else min(d, 31)
+                cases.append(v)
+            elif i < 31:
+                for j in sorted({i + 1, 31}):
+                    v = [0] * 32
+                    v[i], v[j] = d, 1
+                    cases.append(v)
+    cases.append([-128] * 31 + [1])
+    cases += [[127] * 31 + [t] for t in (0, 1, 31)]
+    cases += [[127 if i % 2 == 0 else -128 for i in range(31)] + [1],
+              [-128 if i % 2 == 0 else 127 for i in range(31)] + [1],
+              [-127 if i % 2 == 0 else 127 for i in range(31)] + [31],
+              [-1] * 31 + [1], [-128] * 31 + [31]]
+    return cases
+
+
+@functools.lru_cache(maxsize=None)
+def scalarmult_base_cases():
+    """-> (k, digits) per case and the expected affine points by Python
+    double-and-add from B (computed once per process)"""
+    import stage_cases as sc
+    r = random.Random(93)
+    digs = scalarmult_base_digit_cases()
+    ks = [sum(d << (8 * i) for i, d in enumerate(v)) for v in digs]
+    ks += [0, 1, L - 1, L, L + 1, 2**252, 2**253 - 1] + [r.randrange(2**253) for _ in range(300)]
+    assert all(0 <= k < 2**253 for k in ks)
+    digs = digs + [py_recode8(k) for k in ks[len(digs):]]
+    assert all(py_recode8(k) == d for k, d in zip(ks, digs))
+    assert sum(1 for d in digs if -128 in d) >= 70 and any(not any(d) for d in digs)
+    B = ed_decode(int.to_bytes(4 * pow(5, P - 2, P) % P, 32, "little"))
+    want = sc.affine_all([sc.double_and_add(k, B) for k in ks])
+    return ks, digs, want
+
+
+def family_scalarmult_base(run):
+    """scalarmult_base over the build's own comb table: the digits recode8 makes
+    are the chosen ones; (X / Z, Y / Z) is [k]B by the oracle's fixed-base
+    multiplication of k mod L and by Python double-and-add; T Z == X Y; every
+    limb inside RED (fe_mul's output bound); ge_p3_tobytes of the point is the
+    oracle's encoding.  -> the number of cases"""
+    import oracle_lib as orc
+    ks, digs, want = scalarmult_base_cases()
+    packed = pl.pack_ints([[k] for k in ks], 32)
+    got_d = np.ascontiguousarray(run("recode8", packed)).view(np.uint32).tolist()
+    out = np.ascontiguousarray(run("scalarmult_base", packed))
+    pts = pl.unpack_limbs(out[:, :160])
+    for k, d, gd, w, c, enc in zip(ks, digs, got_d, want, pts, out[:, 160:]):
+        assert signed_digits(gd, 8) == d, ("recode8", hex(k))
+        assert all(out_ok(f) for f in c), ("limb bound", hex(k), c)
+        ref = orc.scalarmult_base((k % L).to_bytes(32, "little"))
+        assert affine(c) == w == ed_decode(ref), ("scalarmult_base", hex(k), d)
+        assert enc.tobytes() == ref, ("ge_p3_tobytes", hex(k))
+    return len(ks)
+
+
+def ge_p3_tobytes_cases(base_points):
+    """(affine point, X Y Z T limb vectors): [k]B (`base_points`: encodings) and
+    the eight torsion points (x = 0: the identity and the point of order 2, whose
+    y is p - 1; x odd and even), each with Z = 1, a random Z, Z's limbs at
+    +-RED with the other coordinates' limbs pushed outwards, and every
+    coordinate of such a representation multiplied through by one field
+    element (2, p - 1: every coordinate negated, random)"""
+    import stage_cases as sc
+    r = random.Random(97)
+    pts = [ed_decode(b) for b in base_points] + torsion_points()
+    assert {(0, 1), (0, P - 1)} <= set(pts) and {p[0] & 1 for p in pts if p[0]} == {0, 1}
+    cases = []
+    for pt in pts:
+        reps = [[signed_limbs(v) for v in (pt[0], pt[1], 1, pt[0] * pt[1] % P)], extended(r, pt)]
+        for mode in ("scaled", "bound", "bound"):
+            w = sc.ext_limbs(r, pt, mode)
+            reps.append([w[10 * q:10 * q + 10] for q in range(4)])
+        for lam in (2, P - 1, r.randrange(2, P - 1)):
+            scaled = [sc.push_to_red(signed_limbs(val(f) * lam)) for f in reps[r.randrange(len(reps))]]
+            assert all(abs(v) <= RED[i] for f in scaled for i, v in enumerate(f))
+            reps.append(scaled)
+        cases += [(pt, c) for c in reps]
+    return cases
+
+
+def family_ge_p3_tobytes(run, base_points):
+    """ge_p3_tobytes: the canonical encoding (y, x's parity in bit 255) of the
+    affine point, whatever the representation.  -> the number of cases"""
+    cases = ge_p3_tobytes_cases(base_points)
+    for pt, c in cases:
+        assert affine(c) == pt
+    out = run("ge_p3_tobytes", pl.pack_limbs([c for _, c in cases]))
+    for (pt, c), o in zip(cases, out):
+        assert o.tobytes() == ed_encode(pt), ("ge_p3_tobytes", pt, c)
+    return len(cases)

@@ -18,6 +18,12 @@ Measured on MI355X (gfx950), recorded in DESIGN.md section 5:
   half_scalars 0 of 20,068 device results differ bit for bit from the CPU
                build's (not asserted: any (a, b) with the lattice property is
                correct)
+The batch signer's arithmetic (ops 21-24; edv_sign_batch_dev builds every
+benchmark corpus), cases per op: sc_muladd 3,361, recode8 2,082,
+scalarmult_base 563 (the walk over the context's own comb table through the
+sign kernel's GlobalComb view), ge_p3_tobytes 256.  On MI355X: all pass;
+scalarmult_base 1.2 s (the Python double-and-add of its cases), the other
+three at most 0.03 s each.
 """
 import random
 
@@ -42,7 +48,10 @@ def test_probe_rejects_bad_arguments():
     from indy_plenum_amd import edv
     buf = np.zeros(256, np.uint8)
     m = edv.measure_lib()
-    for op, si, so in ((0, 40, 40), (21, 40, 40), (1, 76, 40), (1, 80, 36), (1, 82, 40), (2, 40, 8192)):
+    for op, si, so in ((0, 40, 40), (21, 40, 40), (1, 76, 40), (1, 80, 36), (1, 82, 40), (2, 40, 8192),
+                       (25, 40, 40), (25, 4096, 4096), (-1, 4096, 4096), (21, 92, 32), (21, 96, 28), (22, 28, 32),
+                       (22, 32, 28), (23, 28, 192), (23, 32, 160), (23, 32, 188), (24, 156, 32), (24, 160, 28),
+                       (24, 162, 32)):
         assert m.edv_probe_math(0, op, buf.ctypes.data, si, buf.ctypes.data, so, 1) == edv.EDV_E_ARG
         assert b"probe" in m.edv_last_error()
     assert m.edv_probe_math(0, 1, None, 80, buf.ctypes.data, 40, 1) == edv.EDV_E_ARG
@@ -83,6 +92,23 @@ def test_recode():
 
 def test_ge_frombytes(base_points):
     mc.family_ge_frombytes(pl.device, base_points)
+
+
+def test_sc_muladd():
+    mc.family_sc_muladd(pl.device)
+
+
+def test_recode8():
+    mc.family_recode8(pl.device)
+
+
+def test_scalarmult_base():
+    """the walk over the context's own comb table, read as the sign kernel reads it"""
+    mc.family_scalarmult_base(pl.device)
+
+
+def test_ge_p3_tobytes(base_points):
+    mc.family_ge_p3_tobytes(pl.device, base_points)
 
 
 def test_half_scalars():

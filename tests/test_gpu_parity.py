@@ -310,6 +310,88 @@ def test_device_resident_entry_point():
     assert np.array_equal(acc.download(2000), want[1000:])
 
 
+MSG_BASES = (0, 2**32 - 1, 2**32 + 5, 2**40 + 3)
+
+
+def _with_bases(off):
+    """The offset array shifted by each msg_base, uploaded; the data pointers stay."""
+    out = []
+    for base in MSG_BASES:
+        o = off + np.uint64(base)
+        b = edv.DeviceBuffer(o.nbytes)
+        b.upload(o)
+        out.append((base, b))
+    return out
+
+
+def test_msg_base_above_2_to_32_on_every_device_entry_point(latency_limit):
+    """A C3 shard passes global offsets with its msg_base: 64-bit, and above
+    2^32 once 16 M requests carry more than 256 B.  Every device-resident entry
+    point computes off[i] - msg_base itself, in every kernel family: one
+    600-request batch of varied lengths (200..4,096 B, a fifth damaged) with
+    msg_base 0, 2^32 - 1, 2^32 + 5 and 2^40 + 3 (the offsets shifted by as much,
+    the message pointer unchanged) through verify_device on the right-to-left
+    latency kernel, on the batch kernels (length buckets forced, left to the
+    device mode, and off), verify_device_pipelined, sha256_device and
+    sign_device; 4,097 requests once for the two-walk latency kernel.  Every
+    result equals the checker's, hashlib's and the signing golden's, at every
+    base: 600 x 4 x 5 + 4,097 x 4 verdicts, 600 x 4 digests, 600 x 4 signatures."""
+    N = 4097
+    sigs, pks, msgs, off = orc.corpus(0xB45E, 0, N, mode=1, invalid_permille=200)
+    want = checker(sigs, pks, msgs, off)
+    assert 0 < want[:600].sum() < 600
+    ds, dp, dm = (edv.DeviceBuffer(a.nbytes + 64) for a in (sigs, pks, msgs))
+    for b, a in zip((ds, dp, dm), (sigs, pks, msgs)):
+        b.upload(a)
+    acc = edv.DeviceBuffer(N)
+    seven = np.full(N, 7, np.uint8)
+
+    def verdicts(n, run):
+        acc.upload(seven)
+        run()
+        return acc.download(n)
+
+    runs = [("latency, right-to-left", edv.LATENCY_PATH_DEFAULT, 600, 0, False),
+            ("latency, two-walk", edv.LATENCY_PATH_DEFAULT, N, 0, False),
+            ("batch, buckets", 0, 600, edv.FLAG_BUCKETS, False),
+            ("batch, device mode", 0, 600, 0, False),
+            ("batch, uniform hint", 0, 600, edv.FLAG_UNIFORM_LENGTH, False),
+            ("pipelined", 0, 600, 0, True)]
+    for what, limit, n, flags, pipelined in runs:
+        latency_limit(limit)
+        for base, dob in _with_bases(off[:n + 1]):
+            if pipelined:
+                def run():
+                    edv.verify_device_pipelined(ds.ptr, dp.ptr, dm.ptr, dob.ptr, n, acc.ptr, msg_base=base, flags=flags)
+                    edv.pipeline_sync(0)
+            else:
+                def run():
+                    edv.verify_device(ds.ptr, dp.ptr, dm.ptr, dob.ptr, n, acc.ptr, msg_base=base, flags=flags)
+            got = verdicts(n, run)
+            assert np.array_equal(got, want[:n]), (what, base, np.nonzero(got != want[:n])[0][:8].tolist())
+    # SHA-256 of the same 600 messages
+    digests = b"".join(hashlib.sha256(msgs[int(off[i]):int(off[i + 1])].tobytes()).digest() for i in range(600))
+    dd = edv.DeviceBuffer(32 * 600)
+    for base, dob in _with_bases(off[:601]):
+        dd.upload(np.full(32 * 600, 7, np.uint8))
+        edv.sha256_device(dm.ptr, dob.ptr, 600, dd.ptr, msg_base=base)
+        assert dd.download(32 * 600).tobytes() == digests, base
+    # the signer, on the first 600 libsodium signing vectors
+    vec = golden_io.load_sign_golden()[:600]
+    seeds, smsgs, soff = golden_io.pack_sign_batch(vec)
+    assert len(vec) == 600 and len({len(r[1]) for r in vec}) > 50
+    dseed, dsm = edv.DeviceBuffer(len(seeds) + 64), edv.DeviceBuffer(len(smsgs) + 64)
+    dseed.upload(np.frombuffer(seeds, np.uint8))
+    dsm.upload(np.frombuffer(smsgs + b"\0" * 16, np.uint8))
+    dpk, dsig = edv.DeviceBuffer(32 * 600), edv.DeviceBuffer(64 * 600)
+    for base, dob in _with_bases(soff):
+        dpk.upload(np.full(32 * 600, 7, np.uint8))
+        dsig.upload(np.full(64 * 600, 7, np.uint8))
+        edv.sign_device(dseed.ptr, dsm.ptr, dob.ptr, 600, dpk.ptr, dsig.ptr, msg_base=base)
+        assert dpk.download(32 * 600).tobytes() == b"".join(r[2] for r in vec), base
+        assert dsig.download(64 * 600).tobytes() == b"".join(r[3] for r in vec), base
+
+
 def test_device_mask_selects_device():
     sigs, pks, msgs, off = orc.corpus(0xE1, 0, 1000, mode=0, invalid_permille=300)
     want = checker(sigs, pks, msgs, off)

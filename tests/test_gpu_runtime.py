@@ -128,6 +128,38 @@ def test_device_entry_points_reject_misaligned_pointers():
     assert acc.download(64).all()
 
 
+def test_sha256_device_entry_point_rejects_null_and_misaligned_pointers():
+    """edv_sha256_batch_dev: EDV_E_ARG before anything reaches the GPU for a
+    null d_msgs / d_msg_off / d_out with n > 0 (a null d_msgs even when every
+    message is empty), a d_msg_off off its 8-byte and a d_out off its 16-byte
+    alignment (the kernel stores uint4); the output keeps its sentinel; n = 0
+    with nulls, an unaligned d_msgs and aligned buffers all still work."""
+    import hashlib
+    lib = edv.lib()
+    msgs = np.frombuffer(b"\x5a" + b"abc" + b"defgh" + b"\0" * 64, np.uint8)
+    off = np.array([1, 4, 4, 9], np.uint64)
+    dm, do = _upload(msgs, off)
+    dd = edv.DeviceBuffer(32 * 3 + 64)
+    sent = np.full(32 * 3 + 64, 0xA5, np.uint8)
+    dd.upload(sent)
+    empty = edv.DeviceBuffer(64)
+    empty.upload(np.zeros(8, np.uint64).view(np.uint8))          # three empty messages
+    for args in ((None, do.ptr, 3, dd.ptr), (dm.ptr, None, 3, dd.ptr), (dm.ptr, do.ptr, 3, None),
+                 (None, empty.ptr, 3, dd.ptr),
+                 (dm.ptr, do.ptr + 4, 3, dd.ptr), (dm.ptr, do.ptr + 1, 3, dd.ptr),
+                 (dm.ptr, do.ptr, 3, dd.ptr + 8), (dm.ptr, do.ptr, 3, dd.ptr + 4), (dm.ptr, do.ptr, 3, dd.ptr + 1),
+                 (dm.ptr, do.ptr + 4, 0, dd.ptr), (dm.ptr, do.ptr, 0, dd.ptr + 8)):
+        d_msgs, d_off, n, d_out = args
+        assert lib.edv_sha256_batch_dev(d_msgs, d_off, 0, n, d_out, 0, None) == edv.EDV_E_ARG, args
+        assert b"sha256" in lib.edv_last_error()
+    assert np.array_equal(dd.download(len(sent)), sent)
+    assert lib.edv_sha256_batch_dev(None, None, 0, 0, None, 0, None) == edv.EDV_OK
+    edv.sha256_device(dm.ptr + 1, do.ptr, 3, dd.ptr + 16, msg_base=1)   # d_msgs may have any alignment
+    got = dd.download(len(sent))
+    assert got[16:112].tobytes() == b"".join(hashlib.sha256(m).digest() for m in (b"abc", b"", b"defgh"))
+    assert np.array_equal(got[:16], sent[:16]) and np.array_equal(got[112:], sent[112:])
+
+
 @pytest.mark.parametrize("n", [1, 255, 4097, 65536 + 77])
 def test_host_path_pinned_and_pageable(n):
     sigs, pks, msgs, off = orc.corpus(0x9E + n, 0, n, mode=n % 2, invalid_permille=150)

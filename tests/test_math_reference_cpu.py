@@ -70,6 +70,23 @@ def test_ge_frombytes():
     mc.family_ge_frombytes(pl.host, base_points())
 
 
+def test_sc_muladd():
+    assert mc.family_sc_muladd(pl.host) == 3361
+
+
+def test_recode8():
+    assert mc.family_recode8(pl.host) == 2082
+
+
+def test_scalarmult_base():
+    """the CPU build walks HostComb, the table hc_comb_entries reads back"""
+    assert mc.family_scalarmult_base(pl.host) == 563
+
+
+def test_ge_p3_tobytes():
+    assert mc.family_ge_p3_tobytes(pl.host, base_points()) == 32 * 8
+
+
 def test_single_case_wrappers_agree_with_the_packed_probe():
     """hc_approx_div, hc_fdiv_floor, hc_euclid_div, hc_recode5_windows and
     hc_ge_frombytes_negate_limbs are the packed ops' functions"""
