@@ -168,6 +168,57 @@ int edv_sha256_batch_dev(const uint8_t *d_msgs, const uint64_t *d_msg_off, uint6
                          uint8_t *d_out, int device, void *stream);
 
 /*
+ * Ledger Merkle tree (row f-5): extend a compact RFC 6962 tree by a batch of
+ * leaves in one call, bit-exact with n successive appends of the reference's
+ * CompactMerkleTree (ledger/compact_merkle_tree.py:155-191 over
+ * ledger/tree_hasher.py:20-28, called per transaction by
+ * ledger/ledger.py:145-148).  Leaf hash SHA-256(0x00 | leaf), node hash
+ * SHA-256(0x01 | left | right), empty root SHA-256("").
+ *
+ * A tree is (size, hashes): the roots of the full subtrees of the binary
+ * decomposition of size, largest first, popcount(size) x 32 bytes.  With
+ * new = old_size + n the call writes
+ *   leaf_hashes  n x 32 bytes, in order (NULL: not wanted)
+ *   node_hashes  the interior nodes in the order the appends create them
+ *                (leaf s, 1-based, writes heights 1 .. ctz(s), ascending):
+ *                (new - popcount(new)) - (old - popcount(old)) x 32 bytes, the
+ *                node-store positions after the old tree's (NULL: not wanted)
+ *   new_hashes   popcount(new) x 32 bytes (at most 63 entries)
+ *   root         32 bytes
+ * n = 0 is valid (hashes copied, root folded).  leaves / leaf_off are laid out
+ * as msgs / msg_off everywhere else: n + 1 non-decreasing offsets.
+ * EDV_E_ARG before anything is launched or written: n above
+ * EDV_MERKLE_MAX_LEAVES, old_size + n above 2^62, old_size > 0 with NULL
+ * old_hashes, NULL new_hashes / root, NULL leaf_off (or leaves, unless every
+ * leaf is empty) with n > 0, offsets that decrease.
+ * Host form: synchronous on `device`, staged in buffers of its own; only the
+ * outputs asked for are copied back.  The scratch (tile roots handed from one
+ * pass of eight heights to the next) and the staging grow by use, count in
+ * edv_context_memory out[2], and are freed by edv_trim (what a batch of
+ * keep_batch leaves does not need; all for 0) and edv_release.  A process that
+ * never calls these two allocates nothing for them.
+ */
+#define EDV_MERKLE_MAX_LEAVES (1ull << 22)
+int edv_merkle_extend(uint64_t old_size, const uint8_t *old_hashes,
+                      const uint8_t *leaves, const uint64_t *leaf_off, uint64_t n,
+                      uint8_t *leaf_hashes, uint8_t *node_hashes,
+                      uint8_t *new_hashes, uint8_t *root, int device);
+/* Device-resident form, async on `stream` (NULL = library stream, synchronised
+ * before returning); offsets are absolute into d_leaves minus leaf_base.
+ * d_leaves may have any alignment and must be readable 8 bytes past the last
+ * leaf byte; nothing below the aligned 32-bit word holding a leaf's first byte
+ * is read.  Also EDV_E_ARG, with nothing launched: d_leaf_off not 8-byte
+ * aligned, any hash buffer (d_old_hashes, d_leaf_hashes, d_node_hashes,
+ * d_new_hashes, d_root) not 16-byte aligned, n > 0 with NULL d_leaves or
+ * d_leaf_off (the offsets live in device memory and are not checked).  The
+ * output buffers must not overlap d_old_hashes.  Calls on different streams
+ * are ordered on the shared scratch by an event, as the verify launches are. */
+int edv_merkle_extend_dev(uint64_t old_size, const uint8_t *d_old_hashes,
+                          const uint8_t *d_leaves, const uint64_t *d_leaf_off, uint64_t leaf_base, uint64_t n,
+                          uint8_t *d_leaf_hashes, uint8_t *d_node_hashes,
+                          uint8_t *d_new_hashes, uint8_t *d_root, int device, void *stream);
+
+/*
  * Pipelined submission of device-resident batches (a continuous stream of
  * client batches, e.g. one per Node prod): enqueues the batch and returns
  * without waiting.  Consecutive submissions alternate between two internal
@@ -280,7 +331,8 @@ int edv_context_count(void);
 /*
  * Device memory the library holds for `device` in this process, in bytes:
  * out[0] total, out[1] the [S]B tables (shared by the logical devices of one
- * GPU), out[2] chunk scratch of the ordinary paths, out[3] the asynchronous
+ * GPU), out[2] chunk scratch of the ordinary paths and the Merkle-tree
+ * extension's scratch and staging, out[3] the asynchronous
  * slots (inputs and small-batch scratch), out[4] the pipelined state sets,
  * out[5] input buffers of the synchronous path, out[6] the signer's comb
  * table.  Scratch grows with the largest batch seen (up to one chunk), so a

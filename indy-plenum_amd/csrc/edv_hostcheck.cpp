@@ -8,6 +8,7 @@
 #include <vector>
 #include "edv_verify_core.h"
 #include "edv_sha256.h"
+#include "edv_merkle.h"
 #include "edv_ledger.h"
 #include "edv_tables.h"
 #include "edv_selftest_cases.h"
@@ -563,6 +564,88 @@ int hc_verify_batch(const uint8_t* sigs, const uint8_t* pks, const uint8_t* msgs
     HostBStage bs{bt};
     accept[i] = verify_one(R, S, A, buf.data() + 16, mlen, at, rt, bs) ? 1 : 0;
   }
+  return 0;
+}
+
+// ---- the Merkle-tree extension (edv_merkle.h, row f-5)
+// out: kMerkleLogT, kMerkleT, kMerkleMaxHashes
+void hc_merkle_consts(int32_t* out) { out[0] = kMerkleLogT; out[1] = kMerkleT; out[2] = kMerkleMaxHashes; }
+uint64_t hc_merkle_store_pos(int h, uint64_t k) { return merkle_store_pos(h, k); }
+uint64_t hc_merkle_node_count(uint64_t s) { return merkle_node_count(s); }
+// the prefixed loader on a leaf that starts `misalign` bytes into a word, the
+// word before the leaf's first one not addressable through the buffer
+void hc_merkle_leaf_hash(const uint8_t* m, uint64_t mlen, int misalign, uint8_t* out32) {
+  std::vector<uint32_t> buf((mlen + 3 + 8) / 4 + 1, 0xA5A5A5A5u);
+  uint8_t* p = reinterpret_cast<uint8_t*>(buf.data()) + (misalign & 3);
+  if (mlen) memcpy(p, m, mlen);
+  uint32_t H[8], o[8];
+  merkle_leaf_hash(H, p, mlen);
+  merkle_store_hash(o, H);
+  store_words(out32, o, 8);
+}
+// edv_merkle_extend's signature minus `device`: the kernels' passes and tiles,
+// lanes and levels run one after another (what __syncthreads() separates on
+// the device is a finished loop here).
+int hc_merkle_extend(uint64_t old_size, const uint8_t* old_hashes, const uint8_t* leaves, const uint64_t* off,
+                     uint64_t n, uint8_t* leaf_hashes, uint8_t* node_hashes, uint8_t* new_hashes, uint8_t* root) {
+  if (old_size > kMerkleMaxSize || n > kMerkleMaxSize || old_size + n > kMerkleMaxSize) return -1;
+  if ((old_size && !old_hashes) || !new_hashes || !root || (n && !off)) return -1;
+  for (uint64_t i = 0; i < n; i++)
+    if (off[i + 1] < off[i]) return -1;
+  const uint64_t new_size = old_size + n;
+  const uint64_t nodes = merkle_node_count(new_size) - merkle_node_count(old_size);
+  const uint64_t mbase = n ? off[0] : 0, mbytes = n ? off[n] - off[0] : 0;
+  // the leaves keep their alignment relative to their offsets; 8 readable bytes past the end
+  std::vector<uint32_t> lbuf((mbytes + 3 + 8) / 4 + 2, 0);
+  uint8_t* lv = reinterpret_cast<uint8_t*>(lbuf.data()) + (mbase & 3);
+  if (mbytes) memcpy(lv, leaves + mbase, mbytes);
+  std::vector<uint32_t> oldw(8 * size_t(popc64(old_size)) + 8), neww(8 * size_t(popc64(new_size)) + 8), rootw(8);
+  if (old_size) memcpy(oldw.data(), old_hashes, 32 * size_t(popc64(old_size)));
+  std::vector<uint32_t> leafw(leaf_hashes ? 8 * n : 0), nodew(node_hashes ? 8 * nodes : 0);
+  std::vector<uint32_t> roots(8 * merkle_scratch_hashes(old_size, new_size) + 8);
+  MerklePass a;
+  a.old_size = old_size;
+  a.new_size = new_size;
+  a.old_hashes = oldw.data();
+  a.leaf_out = leaf_hashes ? leafw.data() : nullptr;
+  a.node_out = node_hashes ? nodew.data() : nullptr;
+  a.new_hashes = neww.data();
+  a.in = nullptr;
+  uint32_t* rp = roots.data();
+  std::vector<uint32_t> lvl0(8 * kMerkleT), lvl1(8 * kMerkleT);
+  uint32_t* lvl[2] = {lvl0.data(), lvl1.data()};
+  for (int h0 = 0; merkle_pass_runs(old_size, new_size, h0); h0 += kMerkleLogT) {
+    const uint64_t next_items =
+        merkle_pass_runs(old_size, new_size, h0 + kMerkleLogT) ? merkle_pass_items(old_size, new_size, h0 + kMerkleLogT) : 0;
+    a.h0 = h0;
+    a.roots_out = next_items ? rp : nullptr;
+    const uint64_t tile0 = merkle_pass_first_tile(old_size, h0), tiles = merkle_pass_tiles(old_size, new_size, h0);
+    for (uint64_t tile = tile0; tile < tile0 + tiles; tile++) {
+      for (uint32_t w = 0; w < 8 * kMerkleT; w++) lvl0[w] = lvl1[w] = 0xDEADBEEFu;  // nothing stale may be read
+      for (uint32_t j = 0; j < uint32_t(kMerkleT); j++) {
+        uint64_t g;
+        if (!merkle_item_index(a, tile, j, &g)) continue;
+        uint32_t H[8];
+        if (h0 == 0) {
+          const uint64_t i = g - old_size;
+          merkle_leaf_hash(H, lv + (off[i] - mbase), off[i + 1] - off[i]);
+        } else {
+          merkle_load_hash(H, a.in + 8 * (g - (old_size >> h0)));
+        }
+        merkle_item_put(a, g, j, H, lvl[0]);
+      }
+      for (int hl = 1; hl <= kMerkleLogT; hl++)
+        for (uint32_t j = 0; j < (uint32_t(kMerkleT) >> hl); j++)
+          merkle_level(a, tile, hl, j, lvl[(hl - 1) & 1], lvl[hl & 1]);
+    }
+    a.in = rp;
+    rp += 8 * next_items;
+  }
+  merkle_finish(old_size, new_size, a.old_hashes, a.new_hashes, rootw.data());
+  if (leaf_hashes && n) memcpy(leaf_hashes, leafw.data(), 32 * n);
+  if (node_hashes && nodes) memcpy(node_hashes, nodew.data(), 32 * nodes);
+  memcpy(new_hashes, neww.data(), 32 * size_t(popc64(new_size)));
+  memcpy(root, rootw.data(), 32);
   return 0;
 }
 }

@@ -35,5 +35,13 @@ constexpr uint64_t kRtlMax = 4096;
 hipError_t launch_pack_bits_kernel(hipStream_t s, const uint8_t* acc, uint64_t n, uint8_t* bits);
 hipError_t launch_sha256_kernel(unsigned blocks, hipStream_t s, const uint8_t* msgs, const uint64_t* off,
                                 uint64_t msg_base, uint64_t n, uint32_t* out);
+// Merkle-tree extension (edv_merkle.hip; MerklePass: edv_merkle.h): one pass
+// over all its tiles (pass 0 hashes the leaves; no launch for a pass without
+// items), and the finish (kept entries of the new hashes, root)
+struct MerklePass;
+hipError_t launch_merkle_pass_kernel(hipStream_t s, const MerklePass& a, const uint8_t* leaves, const uint64_t* off,
+                                     uint64_t leaf_base);
+hipError_t launch_merkle_finish_kernel(hipStream_t s, uint64_t old_size, uint64_t new_size, const uint32_t* old_hashes,
+                                       uint32_t* new_hashes, uint32_t* root);
 
 }  // namespace edv

@@ -1,0 +1,300 @@
+// edv_merkle.h -- extending a compact RFC 6962 Merkle tree by a batch of leaves
+// (SURVEY.md section 8f row f-5).
+//
+// Replaces, per batch of transactions:
+//   ledger/ledger.py:145-148              Ledger._addToTree (one append per txn)
+//   ledger/compact_merkle_tree.py:155-191 CompactMerkleTree.append / extend
+//   ledger/tree_hasher.py:20-28           hash_leaf = sha256(0x00 | leaf),
+//                                         hash_children = sha256(0x01 | l | r)
+//
+// A tree of `size` leaves is (size, hashes): the roots of the full subtrees of
+// the binary decomposition of size, largest first.  Extending `old` leaves by n
+// gives, for every height h >= 1, the new aligned blocks k in
+// [old >> h, new >> h) (block k covers leaves [k 2^h, (k + 1) 2^h)); the only
+// child of a new block that is not itself new is the left child of block
+// old >> h when bit h - 1 of old is set: the old tree's entry for that bit.
+//
+// The work is cut into passes of kMerkleLogT heights.  Pass p works on items
+// of height h0 = p kMerkleLogT (leaves in pass 0, the roots of the previous
+// pass's complete tiles after it); a tile is kMerkleT consecutive item indices
+// aligned to kMerkleT, reduced level by level in a pair of buffers (LDS on the
+// device).  Everything here is __host__ __device__: the kernels
+// (edv_merkle.hip) and the CPU harness (edv_hostcheck.cpp, hc_merkle_extend)
+// are loops over these functions, so the straddling-tile and multi-pass logic
+// is tested without a GPU.
+//
+// Hashes in memory are their 32 bytes (read and written as little-endian
+// words); in the level buffers they are the eight big-endian state words.
+#pragma once
+#include <stdint.h>
+
+#include "edv_sha256.h"
+
+namespace edv {
+
+constexpr int kMerkleLogT = 8;
+constexpr int kMerkleT = 1 << kMerkleLogT;     // items per tile = lanes per workgroup
+constexpr int kMerkleMaxHashes = 63;           // popcount(size), size <= 2^62
+constexpr uint64_t kMerkleMaxSize = uint64_t(1) << 62;
+
+EDV_HD int popc64(uint64_t x) { return __builtin_popcountll(x); }
+// x >> h for any h >= 0 (a pass's top level can reach height 64)
+EDV_HD uint64_t shr64(uint64_t x, int h) { return h >= 64 ? 0 : x >> h; }
+
+// ---- index arithmetic
+// interior nodes of a tree of s leaves
+EDV_HD uint64_t merkle_node_count(uint64_t s) { return s - uint64_t(popc64(s)); }
+// 1-based position in the node store of block k at height h >= 1: the appends
+// write heights 1 .. ctz(s) when leaf s = (k + 1) 2^h (1-based) arrives
+EDV_HD uint64_t merkle_store_pos(int h, uint64_t k) {
+  const uint64_t s = (k + 1) << h;
+  return merkle_node_count(s - 1) + uint64_t(h);
+}
+// new blocks at height h: [lo, hi)
+EDV_HD uint64_t merkle_block_lo(uint64_t old_size, int h) { return shr64(old_size, h); }
+EDV_HD uint64_t merkle_block_hi(uint64_t new_size, int h) { return shr64(new_size, h); }
+// index in `hashes` (largest first) of the entry for bit b of size
+EDV_HD int merkle_hashes_index(uint64_t size, int b) { return popc64(shr64(size, b + 1)); }
+// is the left child of new block k at height h the old tree's entry for bit h - 1?
+EDV_HD bool merkle_left_is_old(uint64_t old_size, int h, uint64_t k) {
+  return ((old_size >> (h - 1)) & 1) != 0 && k == shr64(old_size, h);
+}
+// is block k at height h (h = 0: a leaf) an entry of the new tree's hashes?
+EDV_HD bool merkle_is_frontier(uint64_t new_size, int h, uint64_t k) {
+  return h < 64 && ((new_size >> h) & 1) != 0 && k + 1 == (new_size >> h);
+}
+// does the new tree's entry for bit b come unchanged from the old tree?
+EDV_HD bool merkle_frontier_is_old(uint64_t old_size, uint64_t new_size, int b) {
+  return (new_size >> b) == (old_size >> b);
+}
+// items of pass p (height h0): global indices [old >> h0, new >> h0); its
+// tiles: [first, first + count)
+EDV_HD uint64_t merkle_pass_items(uint64_t old_size, uint64_t new_size, int h0) {
+  return shr64(new_size, h0) - shr64(old_size, h0);
+}
+EDV_HD uint64_t merkle_pass_first_tile(uint64_t old_size, int h0) { return shr64(old_size, h0) >> kMerkleLogT; }
+EDV_HD uint64_t merkle_pass_tiles(uint64_t old_size, uint64_t new_size, int h0) {
+  if (merkle_pass_items(old_size, new_size, h0) == 0) return 0;
+  return ((shr64(new_size, h0) - 1) >> kMerkleLogT) - merkle_pass_first_tile(old_size, h0) + 1;
+}
+// does pass h0 have anything to do?  Pass 0 hashes the leaves; a later pass
+// runs only if it has a block one height up (without one there is none higher
+// either: its items are then entries of the new hashes, which the pass before
+// has already written)
+EDV_HD bool merkle_pass_runs(uint64_t old_size, uint64_t new_size, int h0) {
+  return h0 < 64 && merkle_pass_items(old_size, new_size, h0 == 0 ? 0 : h0 + 1) != 0;
+}
+// tile roots every pass after the first reads, all passes together (the scratch)
+EDV_HD uint64_t merkle_scratch_hashes(uint64_t old_size, uint64_t new_size) {
+  uint64_t t = 0;
+  for (int h0 = kMerkleLogT; merkle_pass_runs(old_size, new_size, h0); h0 += kMerkleLogT)
+    t += merkle_pass_items(old_size, new_size, h0);
+  return t;
+}
+
+// ---- hashing
+EDV_HD void merkle_store_hash(uint32_t* dst, const uint32_t H[8]) {  // dst 16-byte aligned on the device
+#if defined(__HIP_DEVICE_COMPILE__)
+  uint4* p = reinterpret_cast<uint4*>(dst);
+  p[0] = make_uint4(bswap32(H[0]), bswap32(H[1]), bswap32(H[2]), bswap32(H[3]));
+  p[1] = make_uint4(bswap32(H[4]), bswap32(H[5]), bswap32(H[6]), bswap32(H[7]));
+#else
+  for (int i = 0; i < 8; i++) dst[i] = bswap32(H[i]);
+#endif
+}
+EDV_HD void merkle_load_hash(uint32_t H[8], const uint32_t* src) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint4* p = reinterpret_cast<const uint4*>(src);
+  const uint4 a = p[0], b = p[1];
+  H[0] = bswap32(a.x); H[1] = bswap32(a.y); H[2] = bswap32(a.z); H[3] = bswap32(a.w);
+  H[4] = bswap32(b.x); H[5] = bswap32(b.y); H[6] = bswap32(b.z); H[7] = bswap32(b.w);
+#else
+  for (int i = 0; i < 8; i++) H[i] = bswap32(src[i]);
+#endif
+}
+EDV_HD void sha256_init(uint32_t H[8]) {
+  H[0] = 0x6a09e667u; H[1] = 0xbb67ae85u; H[2] = 0x3c6ef372u; H[3] = 0xa54ff53au;
+  H[4] = 0x510e527fu; H[5] = 0x9b05688cu; H[6] = 0x1f83d9abu; H[7] = 0x5be0cd19u;
+}
+
+// The 16 big-endian words of block [q0, q0 + 64) of the message P | M, P one
+// byte held in a register: msg_words32_tail's loads and masks over the virtual
+// message that starts one byte before m, except that nothing below the
+// 4-byte-aligned word holding m[0] is loaded (m may be the first byte of an
+// allocation): only word 0 of block 0 could reach there, for its P byte alone,
+// and that byte is put in from the register.  Readable 8 bytes past m + mlen,
+// as sha256_msg asks.
+EDV_HD void msg_words32_prefixed(uint32_t W[16], uint32_t prefix, const uint8_t* m, uint64_t mlen, uint64_t q0) {
+  const uintptr_t m0 = reinterpret_cast<uintptr_t>(m);
+  const uintptr_t a = m0 - 1 + q0;                 // where byte q0 of P | M would sit
+  const uint32_t sh = uint32_t(a & 3);
+  const uintptr_t base = a - sh;
+  const uintptr_t low = m0 & ~uintptr_t(3);
+  const uintptr_t last = (m0 + mlen) & ~uintptr_t(3);  // the word holding the 0x80 pad byte
+  const uint64_t plen = mlen + 1;
+  uint32_t d[17];
+  if (q0 + 64 <= plen) {  // whole block inside P | M: no clamp to the end, no pad
+#pragma unroll
+    for (int t = 0; t < 17; t++) {
+      const uintptr_t p = base + 4 * uintptr_t(t);
+      d[t] = *reinterpret_cast<const uint32_t*>(t == 0 && p < low ? low : p);
+    }
+#pragma unroll
+    for (int t = 0; t < 16; t++) W[t] = bswap32(uint32_t(((uint64_t(d[t + 1]) << 32) | d[t]) >> (8 * sh)));
+  } else {
+    const int32_t lim = int32_t(int64_t(last) - int64_t(base));  // < 0 for a block wholly past the end
+#pragma unroll
+    for (int t = 0; t < 17; t++) {
+      const int32_t back = lim - 4 * t;
+      uintptr_t p = last - uintptr_t(uint32_t(back > 0 ? back : 0));  // min(base + 4 t, last)
+      if (t == 0 && p < low) p = low;
+      d[t] = *reinterpret_cast<const uint32_t*>(p);
+    }
+    const int32_t rem0 = int32_t(int64_t(plen) - int64_t(q0));
+#pragma unroll
+    for (int t = 0; t < 16; t++) {
+      const int32_t r = rem0 - 4 * t;
+      const int32_t nv = r < 0 ? 0 : (r > 4 ? 4 : r);
+      const int32_t nv1 = r + 1 < 0 ? 0 : (r + 1 > 4 ? 4 : r + 1);
+      const uint32_t keep = ((1u << (4 * nv)) << (4 * nv)) - 1u;   // low nv bytes (nv = 4: all)
+      const uint32_t keep1 = ((1u << (4 * nv1)) << (4 * nv1)) - 1u;
+      uint32_t v = uint32_t(((uint64_t(d[t + 1]) << 32) | d[t]) >> (8 * sh));  // little-endian byte order
+      if (t == 0 && q0 == 0) v = (v & ~0xffu) | prefix;
+      v = (v & keep) | ((keep ^ keep1) & 0x80808080u);
+      W[t] = bswap32(v);
+    }
+    return;
+  }
+  if (q0 == 0) W[0] = (W[0] & 0x00ffffffu) | (prefix << 24);
+}
+
+// SHA-256(P | M) -> the eight state words (big-endian order)
+EDV_HD void sha256_prefixed(uint32_t H[8], uint32_t prefix, const uint8_t* m, uint64_t mlen) {
+  sha256_init(H);
+  const uint64_t plen = mlen + 1;
+  const uint64_t nb = (plen + 8 + 1 + 63) / 64;
+  uint32_t W[16];
+#pragma unroll 1
+  for (uint64_t b = 0; b < nb; b++) {
+    msg_words32_prefixed(W, prefix, m, mlen, 64 * b);
+    if (b == nb - 1) {
+      W[14] = uint32_t(plen >> 29);
+      W[15] = uint32_t(plen << 3);
+    }
+    sha256_compress(H, W);
+  }
+}
+// RFC 6962 leaf hash, SHA-256(0x00 | leaf)
+EDV_HD void merkle_leaf_hash(uint32_t H[8], const uint8_t* leaf, uint64_t len) { sha256_prefixed(H, 0u, leaf, len); }
+
+// RFC 6962 node hash, SHA-256(0x01 | l | r): 65 bytes, two blocks spelt out.
+// Block 1 is 0x01, l, r[0..31); block 2 is r[31], 0x80, zeros and the bit
+// length 520.
+EDV_HD void merkle_node_hash(uint32_t H[8], const uint32_t l[8], const uint32_t r[8]) {
+  uint32_t W[16];
+  W[0] = 0x01000000u | (l[0] >> 8);
+#pragma unroll
+  for (int i = 1; i < 8; i++) W[i] = (l[i - 1] << 24) | (l[i] >> 8);
+  W[8] = (l[7] << 24) | (r[0] >> 8);
+#pragma unroll
+  for (int i = 1; i < 8; i++) W[8 + i] = (r[i - 1] << 24) | (r[i] >> 8);
+  const uint32_t tail = (r[7] << 24) | 0x00800000u;
+  sha256_init(H);
+  sha256_compress(H, W);
+  W[0] = tail;
+#pragma unroll
+  for (int i = 1; i < 15; i++) W[i] = 0;
+  W[15] = 520;
+  sha256_compress(H, W);
+}
+EDV_HD void merkle_empty_hash(uint32_t H[8]) {  // SHA-256("")
+  uint32_t W[16];
+  W[0] = 0x80000000u;
+#pragma unroll
+  for (int i = 1; i < 16; i++) W[i] = 0;
+  sha256_init(H);
+  sha256_compress(H, W);
+}
+// Root of (size, hashes): fold from the right
+EDV_HD void merkle_fold(uint32_t root[8], const uint32_t* hashes, int count) {
+  if (count == 0) {
+    merkle_empty_hash(root);
+    return;
+  }
+  merkle_load_hash(root, hashes + 8 * (count - 1));
+#pragma unroll 1
+  for (int i = count - 2; i >= 0; i--) {
+    uint32_t l[8], r[8];
+    merkle_load_hash(l, hashes + 8 * i);
+    for (int w = 0; w < 8; w++) r[w] = root[w];
+    merkle_node_hash(root, l, r);
+  }
+}
+
+// ---- one pass
+struct MerklePass {
+  uint64_t old_size, new_size;  // the call's
+  int h0;                       // height of this pass's items
+  const uint32_t* old_hashes;   // popcount(old_size) entries
+  const uint32_t* in;           // h0 > 0: the items' hashes, item j at 8 (j - (old_size >> h0))
+  uint32_t* leaf_out;           // h0 = 0: leaf hashes, or null
+  uint32_t* node_out;           // node store positions node_count(old) + 1 ..., or null
+  uint32_t* new_hashes;         // the new tree's entries that are new
+  uint32_t* roots_out;          // roots of complete tiles: block k of height h0 + kMerkleLogT at 8 (k - lo), or null
+};
+
+// what becomes of a new hash at height h (0: a leaf), block k
+EDV_HD void merkle_emit(const MerklePass& a, int h, uint64_t k, const uint32_t H[8]) {
+  if (h == 0) {
+    if (a.leaf_out) merkle_store_hash(a.leaf_out + 8 * (k - a.old_size), H);
+  } else if (a.node_out) {
+    merkle_store_hash(a.node_out + 8 * (merkle_store_pos(h, k) - 1 - merkle_node_count(a.old_size)), H);
+  }
+  if (merkle_is_frontier(a.new_size, h, k)) merkle_store_hash(a.new_hashes + 8 * merkle_hashes_index(a.new_size, h), H);
+}
+
+// The level buffers hold word w of local item j at [w kMerkleT + j].
+// Item stage of lane j of a tile (pass 0: H is the lane's leaf hash, by the
+// caller; later passes: loaded here).  False: no such item.
+EDV_HD bool merkle_item_index(const MerklePass& a, uint64_t tile, uint32_t j, uint64_t* g) {
+  *g = (tile << kMerkleLogT) + j;
+  return *g >= shr64(a.old_size, a.h0) && *g < shr64(a.new_size, a.h0);
+}
+EDV_HD void merkle_item_put(const MerklePass& a, uint64_t g, uint32_t j, const uint32_t H[8], uint32_t* cur) {
+  for (int w = 0; w < 8; w++) cur[w * kMerkleT + j] = H[w];
+  if (a.h0 == 0) merkle_emit(a, 0, g, H);  // later passes' items were emitted as the pass before's tile roots
+}
+// Level hl (1 .. kMerkleLogT) of a tile, local block j < kMerkleT >> hl: reads
+// level hl - 1 from cur, writes nxt.
+EDV_HD void merkle_level(const MerklePass& a, uint64_t tile, int hl, uint32_t j, const uint32_t* cur, uint32_t* nxt) {
+  const int h = a.h0 + hl;
+  const uint64_t k = (tile << (kMerkleLogT - hl)) + j;
+  if (k < merkle_block_lo(a.old_size, h) || k >= merkle_block_hi(a.new_size, h)) return;
+  uint32_t l[8], r[8], H[8];
+  if (merkle_left_is_old(a.old_size, h, k)) {
+    merkle_load_hash(l, a.old_hashes + 8 * merkle_hashes_index(a.old_size, h - 1));
+  } else {
+    for (int w = 0; w < 8; w++) l[w] = cur[w * kMerkleT + 2 * j];
+  }
+  for (int w = 0; w < 8; w++) r[w] = cur[w * kMerkleT + 2 * j + 1];
+  merkle_node_hash(H, l, r);
+  for (int w = 0; w < 8; w++) nxt[w * kMerkleT + j] = H[w];
+  merkle_emit(a, h, k, H);
+  if (hl == kMerkleLogT && a.roots_out) merkle_store_hash(a.roots_out + 8 * (k - merkle_block_lo(a.old_size, h)), H);
+}
+
+// Finish: the entries of the new tree's hashes that the old tree already had
+// (same index in both), then the root.
+EDV_HD void merkle_finish(uint64_t old_size, uint64_t new_size, const uint32_t* old_hashes, uint32_t* new_hashes,
+                          uint32_t* root) {
+  for (int b = 62; b >= 0; b--) {
+    if (!((new_size >> b) & 1) || !merkle_frontier_is_old(old_size, new_size, b)) continue;
+    const int i = merkle_hashes_index(new_size, b);
+    for (int w = 0; w < 8; w++) new_hashes[8 * i + w] = old_hashes[8 * i + w];
+  }
+  uint32_t R[8];
+  merkle_fold(R, new_hashes, popc64(new_size));
+  merkle_store_hash(root, R);
+}
+
+}  // namespace edv

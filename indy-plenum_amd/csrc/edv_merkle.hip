@@ -1,0 +1,72 @@
+// edv_merkle.hip -- kernels of the Merkle-tree extension (edv_merkle.h, row
+// f-5), a translation unit of their own so the verify kernels' code does not
+// move.  One workgroup owns one tile of kMerkleT item indices: lane j brings
+// item j in (pass 0: hashes its leaf; later passes: reads the tile root the
+// pass before wrote), then kMerkleLogT levels are reduced in two LDS buffers
+// used in turn, one __syncthreads() per level.  Workgroups never talk to each
+// other: a pass reads what the pass before wrote, and passes are separate
+// launches on one stream.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "edv_merkle.h"
+#include "edv_launch.h"
+
+using namespace edv;
+
+namespace {
+
+template <bool kLeaves>
+__global__ __launch_bounds__(kMerkleT) void edv_merkle_pass_kernel(MerklePass a, uint64_t tile0, const uint8_t* leaves,
+                                                                   const uint64_t* off, uint64_t leaf_base) {
+  __shared__ uint32_t lvl[2][8 * kMerkleT];  // 2 x 8 KiB
+  const uint64_t tile = tile0 + blockIdx.x;
+  const uint32_t j = threadIdx.x;
+  uint64_t g;
+  if (merkle_item_index(a, tile, j, &g)) {
+    uint32_t H[8];
+    if (kLeaves) {
+      const uint64_t i = g - a.old_size;
+      const uint64_t o0 = off[i] - leaf_base, o1 = off[i + 1] - leaf_base;
+      merkle_leaf_hash(H, leaves + o0, o1 - o0);
+    } else {
+      merkle_load_hash(H, a.in + 8 * (g - (a.old_size >> a.h0)));
+    }
+    merkle_item_put(a, g, j, H, lvl[0]);
+  }
+#pragma unroll 1
+  for (int hl = 1; hl <= kMerkleLogT; hl++) {
+    __syncthreads();
+    if (j < (uint32_t(kMerkleT) >> hl)) merkle_level(a, tile, hl, j, lvl[(hl - 1) & 1], lvl[hl & 1]);
+  }
+}
+
+__global__ __launch_bounds__(64) void edv_merkle_finish_kernel(uint64_t old_size, uint64_t new_size,
+                                                               const uint32_t* old_hashes, uint32_t* new_hashes,
+                                                               uint32_t* root) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) merkle_finish(old_size, new_size, old_hashes, new_hashes, root);
+}
+
+}  // namespace
+
+namespace edv {
+
+hipError_t launch_merkle_pass_kernel(hipStream_t s, const MerklePass& a, const uint8_t* leaves, const uint64_t* off,
+                                     uint64_t leaf_base) {
+  const uint64_t tiles = merkle_pass_tiles(a.old_size, a.new_size, a.h0);
+  if (tiles == 0) return hipSuccess;
+  const uint64_t tile0 = merkle_pass_first_tile(a.old_size, a.h0);
+  if (a.h0 == 0)
+    edv_merkle_pass_kernel<true><<<dim3(unsigned(tiles)), dim3(kMerkleT), 0, s>>>(a, tile0, leaves, off, leaf_base);
+  else
+    edv_merkle_pass_kernel<false><<<dim3(unsigned(tiles)), dim3(kMerkleT), 0, s>>>(a, tile0, nullptr, nullptr, 0);
+  return hipGetLastError();
+}
+
+hipError_t launch_merkle_finish_kernel(hipStream_t s, uint64_t old_size, uint64_t new_size, const uint32_t* old_hashes,
+                                       uint32_t* new_hashes, uint32_t* root) {
+  edv_merkle_finish_kernel<<<dim3(1), dim3(64), 0, s>>>(old_size, new_size, old_hashes, new_hashes, root);
+  return hipGetLastError();
+}
+
+}  // namespace edv

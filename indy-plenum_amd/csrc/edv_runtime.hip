@@ -20,6 +20,7 @@
 #include "edv_kernels.h"
 #include "edv_launch.h"
 #include "edv_ledger.h"
+#include "edv_merkle.h"
 #include "edv_tables.h"
 #include "edv_selftest_cases.h"
 #include "../../include/edv.h"
@@ -228,6 +229,16 @@ struct DevCtx {
   hipEvent_t perm_done[2] = {nullptr, nullptr};  // split prep: state set b's bucket permutation is written
   bool pending[2] = {false, false};
   int next = 0;
+  // Merkle-tree extension (edv_merkle_extend[_dev]): nothing of it exists until
+  // the first call.  mk_roots: the tile roots the passes hand on (scratch);
+  // mk_done: recorded after the last kernel that used it, on whatever stream,
+  // and waited for by the next user (as st_done for the verify scratch).  The
+  // other buffers are the host form's staging, its alone while it holds mu.
+  DevBuf mk_roots, mk_leaves, mk_off, mk_hashes, mk_leafh, mk_nodeh;
+  hipEvent_t mk_done = nullptr;
+  uint64_t mk_bytes() const {
+    return mk_roots.cap + mk_leaves.cap + mk_off.cap + mk_hashes.cap + mk_leafh.cap + mk_nodeh.cap;
+  }
 #ifdef EDV_MEASUREMENT_API
   int64_t inject_fail = -1;        // edv_test_fail_async (libedv_measure.so only)
 #endif
@@ -697,6 +708,7 @@ int launch_pipelined(DevCtx& c, const uint8_t* d_sigs, const uint8_t* d_pks, con
 int drain(DevCtx& c) {
   HIPOK(hipStreamSynchronize(c.stream), "stream sync");
   HIPOK(hipEventSynchronize(c.st_done), "scratch sync");
+  if (c.mk_done) HIPOK(hipEventSynchronize(c.mk_done), "merkle scratch sync");
   for (int q = 0; q < kQ; q++) HIPOK(hipStreamSynchronize(c.hs[q]), "stream sync");
   if (c.hcp) HIPOK(hipStreamSynchronize(c.hcp), "stream sync");
   if (c.hac) HIPOK(hipStreamSynchronize(c.hac), "stream sync");  // async batches stay pending until edv_wait_async
@@ -1250,6 +1262,82 @@ int run_digest_shard(DevCtx& c, const uint8_t* msgs, const uint64_t* off, uint64
   return 0;
 }
 
+// ---- Merkle-tree extension (edv_merkle.h).  Extends (old_size, d_old) by the
+// n leaves at d_leaves / d_off on stream s: one pass per kMerkleLogT heights
+// while a pass has a block to build, then the finish.  d_leafh / d_nodeh may be null.
+// The tile roots go through c.mk_roots, grown here after its queued users are
+// done; launches on different streams are ordered on it by c.mk_done.  Caller
+// holds c.mu.
+int launch_merkle(DevCtx& c, uint64_t old_size, const uint8_t* d_old, const uint8_t* d_leaves, const uint64_t* d_off,
+                  uint64_t leaf_base, uint64_t n, uint8_t* d_leafh, uint8_t* d_nodeh, uint8_t* d_new, uint8_t* d_root,
+                  hipStream_t s) {
+  const uint64_t new_size = old_size + n;
+  if (!c.mk_done) HIPOK(hipEventCreateWithFlags(&c.mk_done, hipEventDisableTiming), "event");
+  const uint64_t need = 32 * merkle_scratch_hashes(old_size, new_size);
+  if (need > c.mk_roots.cap) {
+    HIPOK(hipEventSynchronize(c.mk_done), "merkle scratch sync");
+    if (c.mk_roots.ensure(need)) return EDV_E_OOM;
+  }
+  if (need) HIPOK(hipStreamWaitEvent(s, c.mk_done, 0), "wait merkle scratch");
+  MerklePass a;
+  a.old_size = old_size;
+  a.new_size = new_size;
+  a.old_hashes = reinterpret_cast<const uint32_t*>(d_old);
+  a.leaf_out = reinterpret_cast<uint32_t*>(d_leafh);
+  a.node_out = reinterpret_cast<uint32_t*>(d_nodeh);
+  a.new_hashes = reinterpret_cast<uint32_t*>(d_new);
+  a.in = nullptr;
+  uint32_t* roots = static_cast<uint32_t*>(c.mk_roots.p);
+  for (int h0 = 0; merkle_pass_runs(old_size, new_size, h0); h0 += kMerkleLogT) {
+    const uint64_t next_items =
+        merkle_pass_runs(old_size, new_size, h0 + kMerkleLogT) ? merkle_pass_items(old_size, new_size, h0 + kMerkleLogT) : 0;
+    a.h0 = h0;
+    a.roots_out = next_items ? roots : nullptr;
+    HIPOK(launch_merkle_pass_kernel(s, a, d_leaves, d_off, leaf_base), "merkle pass launch");
+    a.in = roots;
+    roots += 8 * next_items;
+  }
+  HIPOK(launch_merkle_finish_kernel(s, old_size, new_size, a.old_hashes, a.new_hashes,
+                                    reinterpret_cast<uint32_t*>(d_root)),
+        "merkle finish launch");
+  if (need) HIPOK(hipEventRecord(c.mk_done, s), "record merkle scratch");
+  return 0;
+}
+
+// The host form: staged like run_digest_shard, in buffers of its own; copies
+// back only the outputs asked for.  Caller holds c.mu.
+int run_merkle_host(DevCtx& c, uint64_t old_size, const uint8_t* old_hashes, const uint8_t* leaves, const uint64_t* off,
+                    uint64_t n, uint8_t* leaf_hashes, uint8_t* node_hashes, uint8_t* new_hashes, uint8_t* root) {
+  const uint64_t new_size = old_size + n;
+  const uint64_t nold = uint64_t(popc64(old_size)), nnew = uint64_t(popc64(new_size));
+  const uint64_t nodes = merkle_node_count(new_size) - merkle_node_count(old_size);
+  const uint64_t mbase = n ? off[0] : 0, mbytes = n ? off[n] - off[0] : 0;
+  // mk_hashes: old entries | new entries | root, 32 bytes each
+  if (c.mk_leaves.ensure(mbytes + 64) || c.mk_off.ensure((n + 1) * 8) ||
+      c.mk_hashes.ensure(32 * (2 * kMerkleMaxHashes + 2)) || (leaf_hashes && c.mk_leafh.ensure(32 * n)) ||
+      (node_hashes && c.mk_nodeh.ensure(32 * nodes)))
+    return EDV_E_OOM;
+  const hipStream_t s = c.stream;
+  uint8_t* d_old = static_cast<uint8_t*>(c.mk_hashes.p);
+  uint8_t* d_new = d_old + 32 * kMerkleMaxHashes;
+  uint8_t* d_root = d_new + 32 * kMerkleMaxHashes;
+  if (mbytes) HIPOK(hipMemcpyAsync(c.mk_leaves.p, leaves + mbase, mbytes, hipMemcpyHostToDevice, s), "h2d leaves");
+  if (n) HIPOK(hipMemcpyAsync(c.mk_off.p, off, (n + 1) * 8, hipMemcpyHostToDevice, s), "h2d leaf_off");
+  if (nold) HIPOK(hipMemcpyAsync(d_old, old_hashes, 32 * nold, hipMemcpyHostToDevice, s), "h2d old hashes");
+  uint8_t* d_leafh = leaf_hashes && n ? static_cast<uint8_t*>(c.mk_leafh.p) : nullptr;
+  uint8_t* d_nodeh = node_hashes && nodes ? static_cast<uint8_t*>(c.mk_nodeh.p) : nullptr;
+  int err;
+  if ((err = launch_merkle(c, old_size, d_old, static_cast<uint8_t*>(c.mk_leaves.p), static_cast<uint64_t*>(c.mk_off.p),
+                           mbase, n, d_leafh, d_nodeh, d_new, d_root, s)))
+    return err;
+  if (d_leafh) HIPOK(hipMemcpyAsync(leaf_hashes, d_leafh, 32 * n, hipMemcpyDeviceToHost, s), "d2h leaf hashes");
+  if (d_nodeh) HIPOK(hipMemcpyAsync(node_hashes, d_nodeh, 32 * nodes, hipMemcpyDeviceToHost, s), "d2h node hashes");
+  if (nnew) HIPOK(hipMemcpyAsync(new_hashes, d_new, 32 * nnew, hipMemcpyDeviceToHost, s), "d2h new hashes");
+  HIPOK(hipMemcpyAsync(root, d_root, 32, hipMemcpyDeviceToHost, s), "d2h root");
+  HIPOK(hipStreamSynchronize(s), "stream sync");
+  return 0;
+}
+
 // Asynchronous host path.  Wait for a slot's batch and hand over its verdicts.
 void async_fail(DevCtx& c, DevCtx::AsyncSlot& s) {
   c.ledger.fail(s.ticket);
@@ -1660,6 +1748,13 @@ void trim_buffers(DevCtx& c, uint64_t keep) {
   pin(c.qstage, pinned);
   pin(c.acc_host, k + k / 4 + (k ? 4096 : 0));
   for (int q = 0; q < kQ; q++) pin(c.stage[q], pinned);
+  // the Merkle buffers: what extending any tree by k leaves of kTrimMsgBytes can need
+  dev(c.mk_roots, k ? 32 * (k / (kMerkleT - 1) + 16) : 0);
+  dev(c.mk_leaves, k ? k * kTrimMsgBytes + 64 : 0);
+  dev(c.mk_off, k ? 8 * (k + 1) : 0);
+  dev(c.mk_hashes, k ? 32 * (2 * kMerkleMaxHashes + 2) : 0);
+  dev(c.mk_leafh, 32 * k);
+  dev(c.mk_nodeh, 32 * k);
   for (auto& a : c.as) {
     set(a.cb);
     dev(a.sigs, 64 * k);
@@ -1734,6 +1829,7 @@ void ctx_destroy(DevCtx& c) {
   }
   ev(c.inputs_ready);
   ev(c.st_done);
+  ev(c.mk_done);
   st(c.sp);
   st(c.sm);
   st(c.hcp);
@@ -1900,7 +1996,7 @@ int edv_context_memory(int device, uint64_t out[7]) {
   std::lock_guard<std::mutex> lk(c->mu);
   if (!c->ready) return 0;
   out[1] = shared_tables_bytes(c->phys);
-  out[2] = c->st.bytes();
+  out[2] = c->st.bytes() + c->mk_bytes();
   for (const auto& a : c->as)
     out[3] += a.sigs.cap + a.pks.cap + a.msgs.cap + a.off.cap + a.acc.cap + a.dig.cap + a.cb.bytes() + a.qtab.cap;
   out[4] = c->pst[0].bytes() + c->pst[1].bytes();
@@ -2080,6 +2176,52 @@ int edv_sha256_batch_dev(const uint8_t* d_msgs, const uint64_t* d_msg_off, uint6
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : cl.c->stream;
   int err;
   if ((err = launch_sha256(d_msgs, d_msg_off, msg_base, n, d_out, s))) return err;
+  if (!stream) HIPOK(hipStreamSynchronize(s), "stream sync");
+  return 0;
+}
+
+int edv_merkle_extend(uint64_t old_size, const uint8_t* old_hashes, const uint8_t* leaves, const uint64_t* leaf_off,
+                      uint64_t n, uint8_t* leaf_hashes, uint8_t* node_hashes, uint8_t* new_hashes, uint8_t* root,
+                      int device) {
+  g_err.clear();
+  if (n > EDV_MERKLE_MAX_LEAVES) return set_err(EDV_E_ARG, "merkle: more than EDV_MERKLE_MAX_LEAVES leaves");
+  if (old_size > kMerkleMaxSize || old_size + n > kMerkleMaxSize) return set_err(EDV_E_ARG, "merkle: tree size above 2^62");
+  if (old_size && !old_hashes) return set_err(EDV_E_ARG, "merkle: null old_hashes");
+  if (!new_hashes || !root) return set_err(EDV_E_ARG, "merkle: null new_hashes / root");
+  if (n) {
+    if (!leaf_off) return set_err(EDV_E_ARG, "merkle: null leaf_off");
+    int err;
+    if ((err = check_offsets(leaf_off, n))) return err;
+    if (!leaves && leaf_off[n] != leaf_off[0]) return set_err(EDV_E_ARG, "merkle: null leaves");
+  }
+  CtxLock cl(device);
+  if (cl.err) return cl.err;
+  return run_merkle_host(*cl.c, old_size, old_hashes, leaves, leaf_off, n, leaf_hashes, node_hashes, new_hashes, root);
+}
+
+int edv_merkle_extend_dev(uint64_t old_size, const uint8_t* d_old_hashes, const uint8_t* d_leaves,
+                          const uint64_t* d_leaf_off, uint64_t leaf_base, uint64_t n, uint8_t* d_leaf_hashes,
+                          uint8_t* d_node_hashes, uint8_t* d_new_hashes, uint8_t* d_root, int device, void* stream) {
+  g_err.clear();
+  // before anything reaches the GPU: the kernels read the offsets as 64-bit
+  // words and read and store every hash as two 16-byte vectors
+  if (n > EDV_MERKLE_MAX_LEAVES) return set_err(EDV_E_ARG, "merkle: more than EDV_MERKLE_MAX_LEAVES leaves");
+  if (old_size > kMerkleMaxSize || old_size + n > kMerkleMaxSize) return set_err(EDV_E_ARG, "merkle: tree size above 2^62");
+  if (old_size && !d_old_hashes) return set_err(EDV_E_ARG, "merkle: null d_old_hashes");
+  if (!d_new_hashes || !d_root) return set_err(EDV_E_ARG, "merkle: null d_new_hashes / d_root");
+  if (n && (!d_leaves || !d_leaf_off)) return set_err(EDV_E_ARG, "merkle: null d_leaves / d_leaf_off");
+  if (reinterpret_cast<uintptr_t>(d_leaf_off) & 7) return set_err(EDV_E_ARG, "merkle: d_leaf_off must be 8-byte aligned");
+  for (const uint8_t* p : {d_old_hashes, static_cast<const uint8_t*>(d_leaf_hashes),
+                           static_cast<const uint8_t*>(d_node_hashes), static_cast<const uint8_t*>(d_new_hashes),
+                           static_cast<const uint8_t*>(d_root)})
+    if (reinterpret_cast<uintptr_t>(p) & 15) return set_err(EDV_E_ARG, "merkle: hash buffers must be 16-byte aligned");
+  CtxLock cl(device);
+  if (cl.err) return cl.err;
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : cl.c->stream;
+  int err;
+  if ((err = launch_merkle(*cl.c, old_size, d_old_hashes, d_leaves, d_leaf_off, leaf_base, n, d_leaf_hashes,
+                           d_node_hashes, d_new_hashes, d_root, s)))
+    return err;
   if (!stream) HIPOK(hipStreamSynchronize(s), "stream sync");
   return 0;
 }

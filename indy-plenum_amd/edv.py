@@ -89,6 +89,10 @@ def lib():
         h.edv_sha256_batch.restype = ctypes.c_int
         h.edv_sha256_batch_dev.argtypes = [vp, vp, u64, u64, vp, ctypes.c_int, vp]
         h.edv_sha256_batch_dev.restype = ctypes.c_int
+        h.edv_merkle_extend.argtypes = [u64, vp, vp, vp, u64, vp, vp, vp, vp, ctypes.c_int]
+        h.edv_merkle_extend.restype = ctypes.c_int
+        h.edv_merkle_extend_dev.argtypes = [u64, vp, vp, vp, u64, u64, vp, vp, vp, vp, ctypes.c_int, vp]
+        h.edv_merkle_extend_dev.restype = ctypes.c_int
         h.edv_verify_batch_dev_flags.argtypes = [vp, vp, vp, vp, u64, u64, vp, ctypes.c_int, vp, ctypes.c_uint32]
         h.edv_verify_batch_dev_flags.restype = ctypes.c_int
         h.edv_verify_batch_dev_pipelined.argtypes = [vp, vp, vp, vp, u64, u64, vp, ctypes.c_int, ctypes.c_uint32]
@@ -447,6 +451,67 @@ def pack_bits_device(d_accept, n, d_bits, device=0, stream=None):
 def sha256_device(d_msgs, d_off, n, d_out, device=0, msg_base=0, stream=None):
     """Device-resident batch SHA-256: d_out gets n x 32 bytes."""
     _check(lib().edv_sha256_batch_dev(d_msgs, d_off, msg_base, n, d_out, device, stream))
+
+
+MERKLE_MAX_LEAVES = 1 << 22  # EDV_MERKLE_MAX_LEAVES: leaves per edv_merkle_extend call
+MERKLE_MAX_SIZE = 1 << 62
+
+
+def merkle_node_span(old_size: int, n: int) -> int:
+    """Interior nodes that n appends to a tree of old_size leaves create."""
+    new = old_size + n
+    return (new - bin(new).count("1")) - (old_size - bin(old_size).count("1"))
+
+
+def merkle_extend(old_size: int, old_hashes, leaves, offsets, want_leaf_hashes=True, want_node_hashes=True,
+                  device: int = 0):
+    """Extend the compact RFC 6962 Merkle tree (old_size, old_hashes) by the n
+    leaves laid out as msgs / offsets everywhere else (edv_merkle_extend, row f-5).
+
+    old_hashes: popcount(old_size) x 32 bytes (bytes or uint8 array), largest
+    subtree first.  Returns (leaf_hashes, node_hashes, new_hashes, root):
+    (n, 32), (nodes, 32) and (popcount(new), 32) uint8 arrays and 32 bytes;
+    leaf_hashes / node_hashes are None when not wanted.  Bit-exact with n
+    successive appends of the reference's CompactMerkleTree."""
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    if off.ndim != 1 or len(off) < 1:
+        raise ValueError("offsets must hold n + 1 entries")
+    n = len(off) - 1
+    old_size = int(old_size)
+    if old_size < 0 or old_size + n > MERKLE_MAX_SIZE:
+        raise ValueError("tree size out of range")
+    if n > MERKLE_MAX_LEAVES:
+        raise ValueError("more than MERKLE_MAX_LEAVES leaves in one call")
+    if not isinstance(old_hashes, np.ndarray):
+        old_hashes = np.frombuffer(bytes(old_hashes), dtype=np.uint8)
+    if old_hashes.dtype != np.uint8 or not old_hashes.flags.c_contiguous:
+        raise ValueError("old_hashes must be contiguous uint8")
+    if old_hashes.nbytes != 32 * bin(old_size).count("1"):
+        raise ValueError("old_hashes size does not match old_size")
+    if not isinstance(leaves, np.ndarray):
+        leaves = np.frombuffer(bytes(leaves) or b"\0", dtype=np.uint8)
+    if leaves.dtype != np.uint8 or not leaves.flags.c_contiguous:
+        raise ValueError("leaves must be contiguous uint8")
+    if int(off[-1]) > leaves.nbytes:
+        raise ValueError("offsets exceed the leaf buffer")
+    new_size = old_size + n
+    leaf_h = np.zeros((n, 32), dtype=np.uint8) if want_leaf_hashes else None
+    node_h = np.zeros((merkle_node_span(old_size, n), 32), dtype=np.uint8) if want_node_hashes else None
+    new_h = np.zeros((bin(new_size).count("1"), 32), dtype=np.uint8)
+    root = np.zeros(32, dtype=np.uint8)
+    _check(lib().edv_merkle_extend(old_size, old_hashes.ctypes.data if old_hashes.nbytes else None,
+                                   leaves.ctypes.data, off.ctypes.data, n,
+                                   None if leaf_h is None else leaf_h.ctypes.data,
+                                   None if node_h is None else node_h.ctypes.data,
+                                   new_h.ctypes.data, root.ctypes.data, device))
+    return leaf_h, node_h, new_h, root.tobytes()
+
+
+def merkle_extend_device(old_size, d_old_hashes, d_leaves, d_off, n, d_leaf_hashes, d_node_hashes, d_new_hashes,
+                         d_root, device=0, leaf_base=0, stream=None):
+    """Device-resident form (pointers are ints, None = NULL); async on `stream` if given."""
+    _check(lib().edv_merkle_extend_dev(old_size, d_old_hashes, d_leaves, d_off, leaf_base, n, d_leaf_hashes,
+                                       d_node_hashes, d_new_hashes, d_root, device, stream))
 
 
 def verify_detached_batch(items, device_mask: int = 0):

@@ -1,0 +1,156 @@
+#!/usr/bin/env python3
+"""Times the Merkle-tree extension (row f-5) on the GPU and writes one JSON file
+(default profiles/r07/merkle_bench.json).
+
+For 65,536 leaves of 256 bytes, from old = 0 and from old = 2^20 + 12,345
+(arbitrary frontier bytes):
+  a  edv_merkle_extend_dev            device-resident, all outputs
+  b  edv_sha256_batch_dev             the same leaves (the leaf stage's compressions, no tree)
+  c  edv_sha256_batch_dev             65,536 messages of 65 bytes (the node stage's compressions,
+                                      without the level dependencies)
+  d  edv_merkle_extend                the host-buffer call (staging and copies included)
+  e  CompactMerkleTree.extend(on_device=False)   the host loop
+and (d) against (e) at n = 64 ... 16,384, whose smallest n with d < e is
+MIN_DEVICE_LEAVES (indy_plenum_amd/merkle.py).
+
+Every figure is wall clock around calls that end in a device synchronise (the
+device forms with stream = NULL synchronise the library stream before they
+return), the median of 5 repetitions after a warm-up; a repetition repeats
+the call until it has run for at least --window seconds.  No time is a
+pass/fail gate.  Results of (a) and (d) are compared with (e) before timing.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from indy_plenum_amd import edv, merkle  # noqa: E402
+
+N_BIG = 65536
+LEAF_BYTES = 256
+OLDS = (0, (1 << 20) + 12345)
+SMALL = (64, 256, 1024, 4096, 16384)
+
+
+def timed(fn, window, reps=5):
+    """Median seconds per call over `reps` repetitions of at least `window` seconds each."""
+    fn()  # warm-up: code objects, buffers grown
+    t0 = time.perf_counter()
+    fn()
+    one = max(time.perf_counter() - t0, 1e-6)
+    inner = max(1, int(window / one))
+    out = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        for _ in range(inner):
+            fn()
+        out.append((time.perf_counter() - t0) / inner)
+    return {"median_us": statistics.median(out) * 1e6, "min_us": min(out) * 1e6, "max_us": max(out) * 1e6,
+            "calls_per_repetition": inner, "repetitions": reps}
+
+
+def frontier(rng, size):
+    return rng.integers(0, 256, 32 * bin(size).count("1"), dtype=np.uint8)
+
+
+def dev(a, extra=0):
+    b = edv.DeviceBuffer(max(1, a.nbytes) + extra)
+    if a.nbytes:
+        b.upload(a)
+    return b
+
+
+def host_tree(old, fr, leaves):
+    t = merkle.CompactMerkleTree(tree_size=old, hashes=[fr[i:i + 32].tobytes() for i in range(0, len(fr), 32)])
+    t.extend(leaves, on_device=False)
+    return t
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r07", "merkle_bench.json"))
+    ap.add_argument("--window", type=float, default=0.2)
+    ap.add_argument("--device", type=int, default=0)
+    args = ap.parse_args()
+    if edv.device_count() < 1:
+        sys.exit("bench_merkle needs a gfx950 GPU")
+    rng = np.random.default_rng(0x6962)
+    res = {"leaves": N_BIG, "leaf_bytes": LEAF_BYTES, "window_s": args.window, "version": edv.version(),
+           "big": [], "crossover": []}
+
+    blob = rng.integers(0, 256, N_BIG * LEAF_BYTES + 8, dtype=np.uint8)
+    off = np.arange(N_BIG + 1, dtype=np.uint64) * np.uint64(LEAF_BYTES)
+    leaves = [blob[i * LEAF_BYTES:(i + 1) * LEAF_BYTES].tobytes() for i in range(N_BIG)]
+    d_blob, d_off = dev(blob), dev(off)
+    m65 = rng.integers(0, 256, N_BIG * 65 + 8, dtype=np.uint8)
+    o65 = np.arange(N_BIG + 1, dtype=np.uint64) * np.uint64(65)
+    d_m65, d_o65 = dev(m65), dev(o65)
+    d_dig = edv.DeviceBuffer(32 * N_BIG)
+    for old in OLDS:
+        fr = frontier(rng, old)
+        nodes = edv.merkle_node_span(old, N_BIG)
+        nnew = bin(old + N_BIG).count("1")
+        d_old = dev(fr) if old else None
+        d_lh, d_nh = edv.DeviceBuffer(32 * N_BIG), edv.DeviceBuffer(32 * max(1, nodes))
+        d_new, d_root = edv.DeviceBuffer(32 * 64), edv.DeviceBuffer(32)
+
+        def a():
+            edv.merkle_extend_device(old, d_old.ptr if d_old else None, d_blob.ptr, d_off.ptr, N_BIG, d_lh.ptr,
+                                     d_nh.ptr, d_new.ptr, d_root.ptr, device=args.device)
+
+        def b():
+            edv.sha256_device(d_blob.ptr, d_off.ptr, N_BIG, d_dig.ptr, device=args.device)
+
+        def c():
+            edv.sha256_device(d_m65.ptr, d_o65.ptr, N_BIG, d_dig.ptr, device=args.device)
+
+        def d():
+            return edv.merkle_extend(old, fr, blob, off, device=args.device)
+
+        def e():
+            return host_tree(old, fr, leaves)
+
+        # results first: (a) and (d) equal the host loop
+        t = e()
+        a()
+        lh, nh, new, root = d()
+        assert root == t.root_hash and d_root.download().tobytes() == root
+        assert [bytes(r) for r in new] == list(t.hashes) and d_new.download(32 * nnew).tobytes() == new.tobytes()
+        assert nh.tobytes() == bytes(t.hashStore._nodes) == d_nh.download(32 * nodes).tobytes()
+        assert lh.tobytes() == bytes(t.hashStore._leafs) == d_lh.download().tobytes()
+        row = {"old": old, "a_merkle_extend_dev": timed(a, args.window), "b_sha256_leaves": timed(b, args.window),
+               "c_sha256_65B": timed(c, args.window), "d_merkle_extend_host_buffers": timed(d, args.window),
+               "e_python_host_loop": timed(e, args.window, reps=5)}
+        row["a_over_b_plus_c"] = row["a_merkle_extend_dev"]["median_us"] / (
+            row["b_sha256_leaves"]["median_us"] + row["c_sha256_65B"]["median_us"])
+        res["big"].append(row)
+        print(json.dumps(row), flush=True)
+
+    for n in SMALL:
+        sub_blob = blob[:n * LEAF_BYTES + 8]
+        sub_off = off[:n + 1]
+        sub_leaves = leaves[:n]
+        none = np.zeros(0, np.uint8)
+        row = {"n": n, "old": 0,
+               "d_merkle_extend_host_buffers": timed(lambda: edv.merkle_extend(0, none, sub_blob, sub_off,
+                                                                               device=args.device), args.window),
+               "e_python_host_loop": timed(lambda: host_tree(0, none, sub_leaves), args.window)}
+        row["d_beats_e"] = row["d_merkle_extend_host_buffers"]["median_us"] < row["e_python_host_loop"]["median_us"]
+        res["crossover"].append(row)
+        print(json.dumps(row), flush=True)
+    wins = [r["n"] for r in res["crossover"] if r["d_beats_e"]]
+    res["min_device_leaves"] = min(wins) if wins else None
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print("wrote", args.out)
+
+
+if __name__ == "__main__":
+    main()
