@@ -19,6 +19,7 @@ for an entry is the multiply's input bound, BOUND."""
 import ctypes
 import functools
 import hashlib
+import json
 import os
 import random
 
@@ -322,6 +323,29 @@ def reject_slots(n=PREP_N):
     return slots
 
 
+def expect_request(q):
+    """what the checkers compare a request's state against: the three sides'
+    predicates, h, and the points of both tables"""
+    Rp, Ap = point_of(q["R"]), point_of(q["A"])
+    q["sides"] = (int(q["S"] < L and not small_order(q["R"]) and canonical(q["A"]) and not small_order(q["A"])),
+                  int(canonical(q["A"]) and not small_order(q["A"]) and Ap is not None),
+                  int(canonical(q["R"]) and not small_order(q["R"]) and Rp is not None))
+    q["h"] = int.from_bytes(hashlib.sha512(q["R"] + q["A"] + q["msg"]).digest(), "little") % L
+    q["atab"] = multiples(neg(Ap)) if q["sides"][1] else None
+    # the R side cuts S to 253 bits; B has order L
+    q["rtab"] = multiples(mc.ed_add(base_mult(q["S"] % 2**253), neg(Rp))) if q["sides"][2] else None
+
+
+def pack_requests(reqs):
+    """the requests' bytes in the C-ABI layout (64 spare bytes after the last message)"""
+    off = np.zeros(len(reqs) + 1, np.uint64)
+    off[1:] = np.cumsum([len(q["msg"]) for q in reqs])
+    return {"off": off,
+            "sigs": np.frombuffer(b"".join(q["R"] + q["S"].to_bytes(32, "little") for q in reqs), np.uint8).copy(),
+            "pks": np.frombuffer(b"".join(q["A"] for q in reqs), np.uint8).copy(),
+            "msgs": np.frombuffer(b"".join(q["msg"] for q in reqs) + bytes(64), np.uint8).copy()}
+
+
 @functools.lru_cache(maxsize=None)
 def prep_batch():
     """The 600-request batch: valid signatures over messages of the block-edge
@@ -357,21 +381,11 @@ def prep_batch():
     off[1:] = np.cumsum([len(q["msg"]) for q in reqs])
     assert set(int(o) % 16 for o in off[:-1]) == set(range(16))       # message starts cover every offset mod 16
     assert sha_bucket(8100) == 63 and all(sha_bucket(a) + 1 == sha_bucket(a + 1) for a in (47, 175, 303))
-    for q in reqs:                                                     # what the checkers compare against
-        Rp, Ap = point_of(q["R"]), point_of(q["A"])
-        q["sides"] = (int(q["S"] < L and not small_order(q["R"]) and canonical(q["A"]) and not small_order(q["A"])),
-                      int(canonical(q["A"]) and not small_order(q["A"]) and Ap is not None),
-                      int(canonical(q["R"]) and not small_order(q["R"]) and Rp is not None))
-        q["h"] = int.from_bytes(hashlib.sha512(q["R"] + q["A"] + q["msg"]).digest(), "little") % L
-        q["atab"] = multiples(neg(Ap)) if q["sides"][1] else None
-        # the R side cuts S to 253 bits; B has order L
-        q["rtab"] = multiples(mc.ed_add(base_mult(q["S"] % 2**253), neg(Rp))) if q["sides"][2] else None
+    for q in reqs:
+        expect_request(q)
         q["valid"] = orc.verify(q["R"] + q["S"].to_bytes(32, "little"), q["msg"], q["A"])
     assert sum(q["valid"] for q in reqs) == PREP_N - len(slots) and all(q["kind"] is None or not q["valid"] for q in reqs)
-    return {"reqs": reqs, "off": off,
-            "sigs": np.frombuffer(b"".join(q["R"] + q["S"].to_bytes(32, "little") for q in reqs), np.uint8).copy(),
-            "pks": np.frombuffer(b"".join(q["A"] for q in reqs), np.uint8).copy(),
-            "msgs": np.frombuffer(b"".join(q["msg"] for q in reqs) + bytes(64), np.uint8).copy()}
+    return dict(pack_requests(reqs), reqs=reqs, off=off)
 
 
 def uniform_batch(n=65, mlen=100):
@@ -740,40 +754,231 @@ def check_construction(count=240):
     return len(picked)
 
 
-# ------------------------------------------------------------------ families
-VARIANTS = [(ts, bk, sp) for ts in ("compact", "large") for bk in (False, True) for sp in (False, True)]
+# ------------------------------------------------------------ the edge batch
+# tests/golden/prep_edge_golden.json (make_prep_edge_golden.py): requests built
+# for what the 600 honest requests do not reach in the prep stage and in phase
+# 1 of the latency kernels -- edge entries of the [S]B tables, Q = [S]B - R the
+# identity or of small order, S in [2^252, L), the cut to 253 bits, 32 keys of
+# every kind, accepted signatures whose S has an edge digit -- with libsodium's
+# verdicts.  Each request names the property it was built for (`want`);
+# check_edge_intent asserts it from the request's bytes before anything runs.
+EDGE_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "prep_edge_golden.json")
+EDGE_FAMILIES = ("s_digits", "q_special", "s_canonical", "accepted")
+NAMED_S = {"L-1": L - 1, "L-2": L - 2, "2^252-1": 2**252 - 1, "2^252": 2**252, "2^252+1": 2**252 + 1,
+           "2^253-1": 2**253 - 1}
+
+
+def recode_sb(s, table_set):
+    """The R side's digits of S, from the comment above add_sb (edv_verify_core.h):
+    S is cut to 253 bits; below the top table each digit is the balanced
+    remainder mod 2^bits, in [-half, half), least significant first; what is
+    left over is the top digit, which so keeps the carry from below"""
+    bits, tables = SET_BITS[table_set], SET_TABLES[table_set]
+    half, v, digits = 1 << (bits - 1), s % 2**253, []
+    for _ in range(tables - 1):
+        d = (v + half) % (2 * half) - half
+        digits.append(d)
+        v = (v - d) >> bits
+    digits.append(v)
+    check_recoding(s, table_set, digits)
+    return digits
+
+
+def check_recoding(s, table_set, digits):
+    bits, tables = SET_BITS[table_set], SET_TABLES[table_set]
+    half, cut = 1 << (bits - 1), s % 2**253
+    assert len(digits) == tables
+    assert sum(d << (bits * t) for t, d in enumerate(digits)) == cut, "the digits do not sum back to the value"
+    assert all(-half <= d < half for d in digits[:-1]), "a digit below the top outside [-half, half)"
+    low = sum(d << (bits * t) for t, d in enumerate(digits[:-1]))
+    field = cut >> (bits * (tables - 1))
+    assert digits[-1] == field + (low < 0), "the top digit is its field plus the carry from below"
+    assert 0 <= digits[-1] <= half, "the top digit outside its table"
+
+
+def digit_coverage(batch, table_set):
+    """(zero digits, digits of magnitude half) the R side gathers over the batch's requests"""
+    half = 1 << (SET_BITS[table_set] - 1)
+    ds = [d for q in batch["reqs"] if q["sides"][2] for d in recode_sb(q["S"], table_set)]
+    return sum(1 for d in ds if d == 0), sum(1 for d in ds if abs(d) == half)
+
+
+def sqrt_branch(enc):
+    """Which square root ge_frombytes_negate (edv_math.h) takes for an encoding:
+    with x = u v^3 (u v^7)^((p-5)/8), 0 if v x^2 = u, 1 if v x^2 = -u (x is then
+    multiplied by sqrt(-1)), None if neither (no point)"""
+    y = (int.from_bytes(enc, "little") & M255) % P
+    u, v = (y * y - 1) % P, (D * y * y + 1) % P
+    x = u * pow(v, 3, P) * pow(u * pow(v, 7, P), (P - 5) // 8, P) % P
+    return 0 if (v * x * x - u) % P == 0 else 1 if (v * x * x + u) % P == 0 else None
+
+
+def has_torsion(pt):
+    """[L]pt is not the identity: the point has a component of small order"""
+    return affine_all([double_and_add(L, pt)])[0] != IDENT
+
+
+def order_of(pt):
+    """the order of a point of the torsion subgroup"""
+    for o in (1, 2, 4, 8):
+        if pt == IDENT:
+            return o
+        pt = mc.ed_add(pt, pt)
+    raise AssertionError("not a torsion point")
+
+
+def check_edge_intent(q):
+    """The property the request was built for holds, from its bytes: the digits
+    by recode_sb, ranges and named values by Python integers, Q by affine arithmetic"""
+    w, S, what = q["want"], q["S"], q["kind"]
+    assert q["family"] in EDGE_FAMILIES, what
+    if "digits" in w:
+        digits = recode_sb(S, w["set"])
+        for t, d in w["digits"].items():
+            assert digits[int(t)] == d, (what, "digit", t, digits[int(t)], d)
+        if "others" in w:
+            assert all(d == w["others"] for t, d in enumerate(digits) if str(t) not in w["digits"]), (what, "other digits")
+    if "value" in w:
+        assert S == NAMED_S[w["value"]], (what, "value")
+        if w["value"] == "2^253-1":               # every top digit at its maximum
+            assert all(recode_sb(S, ts)[-1] == 2**253 >> (SET_BITS[ts] * (SET_TABLES[ts] - 1)) for ts in SET_BITS), what
+    if "random" in w:
+        assert S < L, what
+    if "lt_l" in w:
+        assert (S < L) == bool(w["lt_l"]) and q["valid"] == 0, (what, "S < L")
+    if "ge_2_252" in w:
+        assert (S >= 2**252) == bool(w["ge_2_252"]), (what, "S >= 2^252")
+    if "r_mixed" in w:
+        assert has_torsion(point_of(q["R"])) == bool(w["r_mixed"]), (what, "R's order")
+    if "q_order" in w or "q" in w:
+        assert S % 2**253 != 0, what
+        Q = mc.ed_add(base_mult(S % 2**253), neg(point_of(q["R"])))
+        if "q_order" in w:
+            assert order_of(Q) == w["q_order"], (what, "Q's order")
+        else:
+            sb = base_mult(S % 2**253)
+            assert w["q"] == "2sb" and Q == mc.ed_add(sb, sb) and Q != IDENT, (what, "Q = 2 [S]B")
+    if "a_mixed" in w:
+        h = int.from_bytes(hashlib.sha512(q["R"] + q["A"] + q["msg"]).digest(), "little") % L
+        assert has_torsion(point_of(q["A"])) and h % 8 == 0, (what, "mixed-order A with 8 | h")
+    if q["family"] == "accepted":
+        assert q["valid"] == 1 and S < L, (what, "accepted")
+    elif q["family"] in ("s_digits", "s_canonical"):
+        assert q["valid"] == 0, (what, "verdict")
+    assert 0 <= len(q["msg"]) <= 90, (what, "message length")
+
+
+def check_edge_layout(reqs):
+    """the order the fixture promises, and the keys of the s_digits family"""
+    fam = [q["family"] for q in reqs]
+    assert set(fam[:64]) == set(EDGE_FAMILIES), "a family missing from the first wave"
+    assert fam[62] == "q_special" and reqs[62]["want"].get("q_order") == 1, "slot 62: Q the identity"
+    assert fam[63] == "accepted", "slot 63: an accepted case"
+    assert fam[-1] == "s_canonical" and reqs[-1]["S"] >= L, "the last request: S >= L"
+    keys = sorted({q["A"] for q in reqs if q["family"] == "s_digits"})
+    assert len(keys) >= 32, "fewer than 32 distinct keys"
+    B = base_mult(1)
+    assert mc.ed_encode(B) in keys and mc.ed_encode(neg(B)) in keys, "B or -B missing"
+    for mixed in (False, True):
+        grp = [k for k in keys if has_torsion(point_of(k)) == mixed]
+        assert {point_of(k)[0] & 1 for k in grp} == {0, 1}, (mixed, "x parity")
+        assert {sqrt_branch(k) for k in grp} == {0, 1}, (mixed, "square-root branch")
+    for ts in SET_BITS:                      # every table's entry 0 and last entry, on an R side that runs
+        half = 1 << (SET_BITS[ts] - 1)
+        seen = {(t, abs(d)) for q in reqs for t, d in enumerate(recode_sb(q["S"], ts)) if abs(d) in (0, half)}
+        assert {(t, 0) for t in range(SET_TABLES[ts])} <= seen, (ts, "a zero digit missing")
+        assert {(t, half) for t in range(SET_TABLES[ts] - 1)} <= seen, (ts, "an edge digit missing")
+    acc = [q for q in reqs if q["family"] == "accepted"]
+    for ts, ts_t in (("compact", range(16)), ("large", (0, 5, 10))):
+        for d in (0, -(1 << (SET_BITS[ts] - 1))):
+            have = {int(t) for q in acc if q["want"]["set"] == ts for t, x in q["want"]["digits"].items() if x == d}
+            assert have >= set(t for t in ts_t if d == 0 or t < SET_TABLES[ts] - 1), (ts, d, "accepted digits")
+    assert sum(1 for q in acc if "a_mixed" in q["want"]) >= 4
+
+
+def edge_sha256(requests):
+    """the hash the fixture records of its own request list"""
+    return hashlib.sha256(json.dumps(requests, sort_keys=True, separators=(",", ":")).encode()).hexdigest()
 
 
 @functools.lru_cache(maxsize=None)
-def prep_state(backend, n, table_set, buckets, split):
-    """the prep stage's state for the first n requests of the batch (run once per variant)"""
-    return run_prep(backend, prep_batch(), n, table_set, buckets, split)
+def edge_requests():
+    """The fixture's requests and their bytes in the C-ABI layout, each with its
+    family, its intent and libsodium's verdict (`valid`); no expected state yet"""
+    with open(EDGE_GOLDEN) as f:
+        doc = json.load(f)
+    assert doc["sha256"] == edge_sha256(doc["requests"]) and doc["count"] == len(doc["requests"])
+    reqs = [{"R": bytes.fromhex(c["R"]), "S": int.from_bytes(bytes.fromhex(c["S"]), "little"), "A": bytes.fromhex(c["A"]),
+             "msg": bytes.fromhex(c["msg"]), "family": c["family"], "kind": "%s: %s" % (c["family"], c["tag"]),
+             "want": c["want"], "valid": int(c["verdict"])} for c in doc["requests"]]
+    assert sum(q["valid"] for q in reqs) == doc["accepted"]
+    return dict(pack_requests(reqs), reqs=reqs)
 
 
-def family_prep(backend, table_set, buckets, split, n=PREP_N):
-    return check_prep_state(prep_batch(), n, prep_state(backend, n, table_set, buckets, split), buckets)
+@functools.lru_cache(maxsize=None)
+def edge_batch():
+    """The fixture in prep_batch()'s shape: every request's intent asserted,
+    then its expected sides, hash and table points"""
+    b = edge_requests()
+    reqs = [dict(q) for q in b["reqs"]]
+    for q in reqs:
+        check_edge_intent(q)
+    check_edge_layout(reqs)
+    for q in reqs:
+        expect_request(q)
+        assert q["family"] != "s_canonical" or q["sides"][0] == int(q["S"] < L), (q["kind"], "the hash side's bit")
+        assert q["family"] != "accepted" or q["sides"] == (1, 1, 1), q["kind"]
+    return dict(b, reqs=reqs)
 
 
-def family_prep_sizes(backend, n):
+BATCHES = {"prep": prep_batch, "edge": edge_batch}
+
+
+def batch_size(name):
+    return len(BATCHES[name]()["reqs"])
+
+
+# ------------------------------------------------------------------ families
+VARIANTS =[(ts, bk, sp) for ts in ("compact", "large") for bk in (False, True) for sp in (False, True)]
+
+
+@functools.lru_cache(maxsize=None)
+def _prep_state(backend, n, table_set, buckets, split, batch):
+    return run_prep(backend, BATCHES[batch](), n, table_set, buckets, split)
+
+
+def prep_state(backend, n, table_set, buckets, split, batch="prep"):
+    """the prep stage's state for the first n requests of a batch of BATCHES (run once per variant)"""
+    return _prep_state(backend, n, table_set, buckets, split, batch)
+
+
+def family_prep(backend, table_set, buckets, split, n=None, batch="prep"):
+    n = batch_size(batch) if n is None else n
+    return check_prep_state(BATCHES[batch](), n, prep_state(backend, n, table_set, buckets, split, batch), buckets)
+
+
+def family_prep_sizes(backend, n, batch="prep"):
     """a batch size that fills no whole workgroup (or wave), bucketed joint on
     the compact set and unbucketed split on the large one"""
-    family_prep(backend, "compact", True, False, n)
-    family_prep(backend, "large", False, True, n)
+    family_prep(backend, "compact", True, False, n, batch)
+    family_prep(backend, "large", False, True, n, batch)
 
 
-def family_seams(backend, table_set, n=PREP_N):
+def family_seams(backend, table_set, n=None, batch="prep"):
     """split against joint and bucketed against unbucketed: the same state, byte for byte, by request"""
-    ref = by_request(prep_state(backend, n, table_set, False, False), n)
+    n = batch_size(batch) if n is None else n
+    ref = by_request(prep_state(backend, n, table_set, False, False, batch), n)
     for bk, sp in ((False, True), (True, False), (True, True)):
-        got = by_request(prep_state(backend, n, table_set, bk, sp), n)
+        got = by_request(prep_state(backend, n, table_set, bk, sp, batch), n)
         for k in ref:
             assert got[k] == ref[k], (table_set, "buckets" if bk else "", "split" if sp else "", k)
 
 
-def family_sets(backend, n=PREP_N):
+def family_sets(backend, n=None, batch="prep"):
     """the large set and the compact set give the same [S]B - R table points"""
-    same_rtab_points(prep_batch(), n, prep_state(backend, n, "compact", False, False),
-                     prep_state(backend, n, "large", False, False))
+    n = batch_size(batch) if n is None else n
+    same_rtab_points(BATCHES[batch](), n, prep_state(backend, n, "compact", False, False, batch),
+                     prep_state(backend, n, "large", False, False, batch))
 
 
 def family_one_bucket(backend):
@@ -786,10 +991,11 @@ def family_one_bucket(backend):
     assert (acc == 1).all()
 
 
-def family_round_trip(backend, table_set="compact", buckets=True, split=False, prio=False):
-    """prep state -> main stage: the oracle's verdicts for the 600 requests"""
-    b = prep_batch()
-    got = round_trip(backend, b, PREP_N, prep_state(backend, PREP_N, table_set, buckets, split), prio)
+def family_round_trip(backend, table_set="compact", buckets=True, split=False, prio=False, batch="prep"):
+    """prep state -> main stage: the verdicts the batch records for its requests
+    (the oracle's for the 600, libsodium's for the edge batch)"""
+    b, n = BATCHES[batch](), batch_size(batch)
+    got = round_trip(backend, b, n, prep_state(backend, n, table_set, buckets, split, batch), prio)
     assert got == [int(q["valid"]) for q in b["reqs"]]
     return got
 
@@ -1279,22 +1485,29 @@ def check_lat_phase1(kernel, batch, n, st, sb_enc=None):
 
 
 @functools.lru_cache(maxsize=None)
-def lat_phase1_state(backend, kernel, n, table_set):
-    return run_lat_phase1(backend, kernel, prep_batch(), n, table_set)
+def _lat_phase1_state(backend, kernel, n, table_set, batch):
+    return run_lat_phase1(backend, kernel, BATCHES[batch](), n, table_set)
+
+
+def lat_phase1_state(backend, kernel, n, table_set, batch="prep"):
+    return _lat_phase1_state(backend, kernel, n, table_set, batch)
 
 
 @functools.lru_cache(maxsize=None)
-def _sb_encodings():
-    return oracle_base_mults([q["S"] % 2**253 for q in prep_batch()["reqs"]])
+def _sb_encodings(batch="prep"):
+    return oracle_base_mults([q["S"] % 2**253 for q in BATCHES[batch]()["reqs"]])
 
 
-def family_lat_phase1(backend, kernel, table_set, n=PREP_N):
-    return check_lat_phase1(kernel, prep_batch(), n, lat_phase1_state(backend, kernel, n, table_set), _sb_encodings()[:n])
+def family_lat_phase1(backend, kernel, table_set, n=None, batch="prep"):
+    n = batch_size(batch) if n is None else n
+    return check_lat_phase1(kernel, BATCHES[batch](), n, lat_phase1_state(backend, kernel, n, table_set, batch),
+                            _sb_encodings(batch)[:n])
 
 
-def family_lat_sets(backend, kernel, n=PREP_N):
+def family_lat_sets(backend, kernel, n=None, batch="prep"):
     """the two table sets give the same [S]B (limbs may differ) and the same words otherwise"""
-    s1, s2 = (lat_phase1_state(backend, kernel, n, ts) for ts in ("compact", "large"))
+    n = batch_size(batch) if n is None else n
+    s1, s2 = (lat_phase1_state(backend, kernel, n, ts, batch) for ts in ("compact", "large"))
     assert (s1["dig"] == s2["dig"]).all() and (s1["ok"] == s2["ok"]).all() and (s1["pt"][:2] == s2["pt"][:2]).all()
     for s in range(s1["slots"]):
         X1, Y1, Z1, _ = _vals([int(v) for v in s1["pt"][2, :, s]])
@@ -1302,10 +1515,11 @@ def family_lat_sets(backend, kernel, n=PREP_N):
         assert (X1 * Z2 - X2 * Z1) % P == 0 and (Y1 * Z2 - Y2 * Z1) % P == 0 and Z1 and Z2, s
 
 
-def family_lat_round_trip(backend, kernel, table_set="compact", n=PREP_N):
-    """phase-1 out -> walk in: the oracle's verdicts"""
-    st = lat_phase1_state(backend, kernel, n, table_set)
+def family_lat_round_trip(backend, kernel, table_set="compact", n=None, batch="prep"):
+    """phase-1 out -> walk in: the verdicts the batch records (the oracle's; libsodium's for the edge batch)"""
+    n = batch_size(batch) if n is None else n
+    st = lat_phase1_state(backend, kernel, n, table_set, batch)
     got = run_lat_walk(backend, kernel, n, st["dig"], st["pt"], st["ok"])
-    assert got[:n].tolist() == [int(q["valid"]) for q in prep_batch()["reqs"][:n]]
+    assert got[:n].tolist() == [int(q["valid"]) for q in BATCHES[batch]()["reqs"][:n]]
     assert (got[n:] == SENT).all()
     return got[:n].tolist()

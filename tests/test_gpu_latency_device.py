@@ -24,7 +24,11 @@ Measured on MI355X (gfx950), recorded in DESIGN.md section 5:
                is the parent's
   durations    0.94 s / 0.84 s the chosen-state tests (the first use builds the
                cases), 0.86 s the first phase-1 variant, 0.2-0.3 s the other
-               phase-1 variants and the argument rejection, the rest below 0.1 s"""
+               phase-1 variants and the argument rejection, the rest below 0.1 s
+  edge batch   395 requests (400 / 416 slots), both kernels x both table sets at
+               n = 1, 15, 16, 17, 33, 395; 0 of 367 digit-word sets differ from
+               edv_probe_prep_state's; 1.0 s the first test (the oracle's base
+               multiplications), 0.18-0.24 s the others, 2.0 s the 6 edge tests"""
 import numpy as np
 import pytest
 
@@ -120,3 +124,34 @@ def test_latency_round_trip_matches_the_oracle_and_the_product(kernel):
     assert got == edv.verify_arrays(b["sigs"], b["pks"], b["msgs"], b["off"]).tolist()
     for n in (1, 15, 17, 33):
         assert sc.family_lat_round_trip(B, kernel, "compact", n) == got[:n]
+
+
+# ---- the edge batch (tests/golden/prep_edge_golden.json, verdicts by libsodium):
+# phase 1 gathers entry 0 and the last entry of every [S]B table, cuts S in
+# [2^252, L) and above to 253 bits, and pads a tiny batch with an edge request
+E = "edge"
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
+@pytest.mark.parametrize("table_set", ("compact", "large"))
+def test_edge_latency_phase1_state(kernel, table_set):
+    """n = 1, 15, 16, 17, 33 and the whole batch: [S]B against the oracle for
+    every edge S, the padding rule with an edge request repeated, limbs inside
+    RED; then phase 1 out -> walk in gives the fixture's verdicts"""
+    for n in (1, 15, 16, 17, 33, None):
+        sc.family_lat_phase1(B, kernel, table_set, n, batch=E)
+    reqs = sc.edge_batch()["reqs"]
+    got = sc.family_lat_round_trip(B, kernel, table_set, batch=E)
+    assert [i for i, v in enumerate(got) if v] == [i for i, q in enumerate(reqs) if q["family"] == "accepted"]
+    for n in (1, 15, 17, 33, 64):
+        assert sc.family_lat_round_trip(B, kernel, table_set, n, batch=E) == got[:n]
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_edge_latency_table_sets_give_the_same_points(kernel):
+    sc.family_lat_sets(B, kernel, batch=E)
+    n = sc.batch_size(E)
+    st, prep = sc.lat_phase1_state(B, kernel, n, "compact", E), sc.prep_state(B, n, "compact", False, False, E)
+    live = [i for i, q in enumerate(sc.edge_batch()["reqs"]) if q["sides"][0]]
+    print("edge latency phase 1 %s: %d of %d (a, b) digit words differ from edv_probe_prep_state's" %
+          (kernel, sum(1 for i in live if (st["dig"][:, i] != prep["dig"][:, i]).any()), len(live)))

@@ -572,3 +572,82 @@ def test_latency_path_on_corpus_bitmask_slices(latency_limit):
                                                       msgs, off[lo:lo + step + 1])
             mism = np.nonzero(got != want)[0]
             assert mism.size == 0, (name, step, mism[:10].tolist())
+
+
+# ---- the edge batch (tests/golden/prep_edge_golden.json): requests chosen for
+# the prep stage's rare paths, verdicts by libsodium 1.0.18, on every product route
+def _edge():
+    import stage_cases as sc
+    b = sc.edge_requests()
+    want = np.array([q["valid"] for q in b["reqs"]], np.uint8)
+    assert len(want) == 395 and int(want.sum()) == 37
+    assert want.tolist() == [int(q["family"] == "accepted") for q in b["reqs"]]
+    return b["sigs"], b["pks"], b["msgs"], b["off"], want
+
+
+def test_edge_batch_on_every_route(latency_limit):
+    """S with edge digits of both table sets, Q = [S]B - R the identity or of
+    small order, S in [2^252, L) and around L, mixed-order keys, B and -B, and
+    37 accepted signatures with a zero or -half digit: the batch kernels, the
+    right-to-left latency kernel, the two-walk kernel (the batch tiled to 4,097
+    requests), verify_device with EDV_FLAG_BUCKETS and the pipelined entry
+    point all give the fixture's libsodium verdicts, and live libsodium (where
+    present) gives them too."""
+    sigs, pks, msgs, off, want = _edge()
+    n = len(want)
+    if orc.sodium_batch() is not None:
+        assert np.array_equal(orc.sodium_verify_batch(sigs, pks, msgs, off, 16), want)
+    assert orc.verify_batch(sigs.tobytes(), pks.tobytes(), msgs.tobytes(), off, n, 8) == want.tobytes()
+
+    def same(got, want, what):
+        assert np.array_equal(got, want), (what, np.nonzero(got != want)[0][:10].tolist())
+
+    latency_limit(0)
+    same(edv.verify_arrays(sigs, pks, msgs, off), want, "batch kernels")
+    latency_limit(edv.LATENCY_PATH_DEFAULT)
+    same(edv.verify_arrays(sigs, pks, msgs, off), want, "right-to-left kernel")
+    N = 4097
+    times = N // n + 1
+    lens = np.tile(np.diff(off), times)[:N]
+    toff = np.zeros(N + 1, np.uint64)
+    toff[1:] = np.cumsum(lens)
+    tmsgs = np.concatenate([np.tile(msgs[:int(off[-1])], times), np.zeros(64, np.uint8)])
+    same(edv.verify_arrays(np.tile(sigs, times)[:64 * N], np.tile(pks, times)[:32 * N], tmsgs, toff),
+         np.tile(want, times)[:N], "two-walk kernel")
+    bufs = [edv.DeviceBuffer(a.nbytes + 64) for a in (sigs, pks, msgs, off)]
+    for b, a in zip(bufs, (sigs, pks, msgs, off)):
+        b.upload(a)
+    acc = edv.DeviceBuffer(n)
+    latency_limit(0)
+    acc.upload(np.full(n, 7, np.uint8))
+    edv.verify_device(bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr, n, acc.ptr, flags=edv.FLAG_BUCKETS)
+    same(acc.download(n), want, "verify_device, buckets")
+    for flags in (0, edv.FLAG_SPLIT_PREP):
+        acc.upload(np.full(n, 7, np.uint8))
+        edv.verify_device_pipelined(bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr, n, acc.ptr, flags=flags)
+        edv.pipeline_sync(0)
+        same(acc.download(n), want, ("pipelined", flags))
+
+
+def test_edge_batch_under_either_table_policy():
+    """a child process with the compact, then the large table policy set: the
+    edge batch through the latency path and through the batch kernels"""
+    from test_gpu_lifecycle import GiB, child
+    d = child(r'''
+import stage_cases as sc
+b = sc.edge_requests()
+want = np.array([q["valid"] for q in b["reqs"]], np.uint8)
+out["n"] = len(want); out["accepted"] = int(want.sum())
+for name, pol in (("compact", edv.TABLES_COMPACT), ("large", edv.TABLES_LARGE)):
+    edv.set_table_policy(0, pol)
+    for path, limit in (("latency", edv.LATENCY_PATH_DEFAULT), ("batch", 0)):
+        edv.set_latency_path(0, limit)
+        got = edv.verify_arrays(b["sigs"], b["pks"], b["msgs"], b["off"])
+        out[name + "/" + path] = np.nonzero(got != want)[0].tolist()
+    out[name] = edv.table_state(0)
+''')
+    assert d["n"] == 395 and d["accepted"] == 37
+    for k in ("compact/latency", "compact/batch", "large/latency", "large/batch"):
+        assert d[k] == [], (k, d[k][:10])
+    assert d["compact"]["compact_bytes"] > 0 and d["compact"]["large_bytes"] == 0
+    assert d["large"]["large_bytes"] > 3 * GiB

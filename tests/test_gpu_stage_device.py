@@ -16,7 +16,12 @@ Measured on MI355X (gfx950), recorded in DESIGN.md section 5:
   chosen state 1,573 slots (1,183 live walks) through each main kernel
   durations    1.6 s the first chosen-state test (it builds the cases), 1.3 s
                the first prep variant (it builds the batch), 0.5-0.8 s the other
-               prep variants and the table sets, the rest below 0.3 s"""
+               prep variants and the table sets, the rest below 0.3 s
+  edge batch   395 slots per variant (367 pass the hash side); dig, alive and
+               accept equal the CPU build's byte for byte, 0 of 142,200 atab and
+               of 142,200 rtab words differ in each of the 8 variants; 1.3 s the
+               first variant (it builds the expected tables), 0.27-0.33 s the
+               others, 0.15 s a batch size, 4.4 s the 17 edge tests"""
 import numpy as np
 import pytest
 
@@ -134,3 +139,71 @@ def test_large_table_set():
     context if no earlier test of this process has (test_context_memory_and_table_sets
     builds another in the product's context)."""
     sc.family_tables(B, "large")
+
+
+# ---- the edge batch (tests/golden/prep_edge_golden.json, verdicts by libsodium;
+# proven on the CPU build by test_stage_reference_cpu.py): S whose signed digits
+# select entry 0 and the last entry of every [S]B table, Q = [S]B - R the
+# identity or of order 2, 4, 8, S in [2^252, L) and around L, 32 keys of every
+# kind, accepted signatures with an edge digit
+E = "edge"
+
+
+def _words_differing(dev, cpu, n):
+    d, c = sc.by_request(dev, n), sc.by_request(cpu, n)
+    return {k: int((np.frombuffer(d[k], np.int32) != np.frombuffer(c[k], np.int32)).sum()) for k in ("atab", "rtab")}
+
+
+@pytest.mark.parametrize("table_set,buckets,split", sc.VARIANTS)
+def test_edge_prep_state(table_set, buckets, split):
+    """Every word the prep kernel writes for the 395 edge requests (alive,
+    accept, a = b h mod 8L, ranges, the count, every table entry with its limb
+    bound, nothing past n).  On the compact joint variant dig, alive and accept
+    equal the CPU build's byte for byte; the table words that differ are
+    printed, not asserted (any limbs of the same point inside the bound are
+    correct)."""
+    n = sc.batch_size(E)
+    ab = sc.family_prep(B, table_set, buckets, split, batch=E)
+    assert sum(1 for x in ab if x is not None) == sum(q["sides"][0] for q in sc.edge_batch()["reqs"])
+    dev, cpu = (sc.prep_state(bk, n, table_set, buckets, split, E) for bk in (B, "host"))
+    if table_set == "compact" and not split:
+        d, c = sc.by_request(dev, n), sc.by_request(cpu, n)
+        for k in ("dig", "alive", "accept"):
+            assert d[k] == c[k], k
+        if not buckets:
+            for k in ("dig", "alive", "accept"):
+                assert dev[k].tobytes() == cpu[k].tobytes(), k
+    print("edge prep state %s: %d slots, table words differing from the CPU build's: %s of %d each" %
+          ((table_set, buckets, split), n, _words_differing(dev, cpu, n), n * sc.A_WORDS))
+
+
+@pytest.mark.parametrize("n", (1, 63, 64, 65))
+def test_edge_prep_state_batch_sizes(n):
+    """every variant at a size around the wave: slot 62 holds a Q that is the
+    identity, slot 63 an accepted signature with a zero digit"""
+    for table_set, buckets, split in sc.VARIANTS:
+        sc.family_prep(B, table_set, buckets, split, n, batch=E)
+    for table_set in ("compact", "large"):
+        sc.family_seams(B, table_set, n, batch=E)
+    sc.family_sets(B, n, batch=E)
+    d, c = (sc.by_request(sc.prep_state(bk, n, "compact", False, False, E), n) for bk in (B, "host"))
+    assert all(d[k] == c[k] for k in ("dig", "alive", "accept"))
+
+
+@pytest.mark.parametrize("table_set", ("compact", "large"))
+def test_edge_split_and_bucketed_runs_write_the_joint_state(table_set):
+    sc.family_seams(B, table_set, batch=E)
+
+
+def test_edge_large_and_compact_sets_give_the_same_r_points():
+    sc.family_sets(B, batch=E)
+
+
+@pytest.mark.parametrize("prio", (False, True))
+def test_edge_round_trip_matches_libsodium(prio):
+    """the prep state through either main kernel: every accepted case accepted, everything else rejected"""
+    reqs = sc.edge_batch()["reqs"]
+    got = sc.family_round_trip(B, "compact", True, False, prio, batch=E)
+    assert got == sc.family_round_trip(B, "large", False, True, prio, batch=E)
+    assert got == sc.family_round_trip(B, "compact", False, False, prio, batch=E)
+    assert [i for i, v in enumerate(got) if v] == [i for i, q in enumerate(reqs) if q["family"] == "accepted"]

@@ -8,7 +8,10 @@ the chosen states is itself checked by plain double-and-add, and every checker
 is shown to raise on a deliberately wrong value.  The same for the latency
 kernels' families (phase-1 state out, walk on chosen phase-1 states) on the
 CPU references hc_stage_latency_phase1 / hc_stage_latency_walk, before they
-run on the device (test_gpu_latency_device.py)."""
+run on the device (test_gpu_latency_device.py).  The edge batch (the fixture
+tests/golden/prep_edge_golden.json, verdicts by libsodium) goes through the
+same prep and phase-1 families, and every assertion of its builder is shown
+to raise on a wrong expectation."""
 import numpy as np
 import pytest
 
@@ -192,10 +195,142 @@ def test_main_checker_rejects_wrong_verdicts(monkeypatch):
     assert sc.expected_verdict(c) == 0
 
 
+# ---- the edge batch (tests/golden/prep_edge_golden.json, verdicts by libsodium):
+# the fixture, its builder's assertions and the generic checkers on the CPU
+# build, before the same batch runs on the device
+E = "edge"
+KERNELS = ("rtl", "quad")
+
+
+def test_edge_fixture_families_and_coverage():
+    """The fixture as the generator promises it, and the digits the R side
+    gathers: the 600 honest requests reach 1 / 0 zero digits (compact / large)
+    and no digit of magnitude half; the edge batch reaches entry 0 and the
+    last entry of every table of both sets."""
+    b = sc.edge_batch()
+    fam = [q["family"] for q in b["reqs"]]
+    assert {f: fam.count(f) for f in sc.EDGE_FAMILIES} == {"s_digits": 228, "q_special": 108, "s_canonical": 22,
+                                                           "accepted": 37}
+    assert sc.batch_size(E) == 395 and len(b["off"]) == 396 and b["sigs"].size == 64 * 395
+    assert [q["valid"] for q in b["reqs"]] == [int(f == "accepted") for f in fam]
+    assert {q["sides"] for q in b["reqs"]} == {(1, 1, 1), (0, 1, 1)}
+    assert sum(1 for q in b["reqs"] if 2**252 <= q["S"] < L and q["sides"][0]) >= 10
+    assert [sc.digit_coverage(sc.prep_batch(), ts) for ts in ("compact", "large")] == [(1, 0), (0, 0)]
+    cov = {ts: sc.digit_coverage(b, ts) for ts in ("compact", "large")}
+    print("edge batch digit coverage (zero digits, digits of magnitude half):", cov)
+    assert all(z >= 16 * 20 and h >= 60 for z, h in cov.values()), cov
+    # the recoder: the three properties on every S of both batches, and it raises on a wrong digit
+    for q in b["reqs"] + sc.prep_batch()["reqs"]:
+        for ts in ("compact", "large"):
+            sc.recode_sb(q["S"], ts)
+    d = sc.recode_sb(2**252 + 12345, "compact")
+    _raises(lambda: sc.check_recoding(2**252 + 12345, "compact", d[:3] + [d[3] + 1] + d[4:]))
+    _raises(lambda: sc.check_recoding(0x8000, "compact", [0x8000] + [0] * 15))        # half is not below half
+    _raises(lambda: sc.check_recoding(0x8000 << 224, "compact", [0] * 14 + [-0x8000, 0]))
+
+
+@pytest.mark.parametrize("table_set,buckets,split", sc.VARIANTS)
+def test_edge_prep_state(table_set, buckets, split):
+    ab = sc.family_prep(B, table_set, buckets, split, batch=E)
+    assert sum(1 for x in ab if x is not None) == sum(q["sides"][0] for q in sc.edge_batch()["reqs"])
+
+
+@pytest.mark.parametrize("n", (1, 63, 64, 65))
+def test_edge_prep_state_batch_sizes(n):
+    sc.family_prep_sizes(B, n, batch=E)
+
+
+def test_edge_prep_seams_and_sets():
+    for table_set in ("compact", "large"):
+        sc.family_seams(B, table_set, batch=E)
+    sc.family_sets(B, batch=E)
+
+
+def test_edge_round_trip_matches_libsodium():
+    got = sc.family_round_trip(B, "compact", True, False, batch=E)
+    assert got == sc.family_round_trip(B, "large", False, True, batch=E)
+    assert [i for i, v in enumerate(got) if v] == [i for i, q in enumerate(sc.edge_batch()["reqs"]) if q["family"] == "accepted"]
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
+@pytest.mark.parametrize("table_set", ("compact", "large"))
+def test_edge_latency_phase1(kernel, table_set):
+    for n in (1, 15, 16, 17, 33, None):
+        sc.family_lat_phase1(B, kernel, table_set, n, batch=E)
+    sc.family_lat_round_trip(B, kernel, table_set, batch=E)
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_edge_latency_table_sets_give_the_same_points(kernel):
+    sc.family_lat_sets(B, kernel, batch=E)
+
+
+def test_edge_builder_assertions_fire():
+    """Each assertion the edge batch's builder makes raises on a wrong
+    expectation: a digit, a value, a range, Q's order, R's and A's order, the
+    verdict, the order of the batch; and the generic checker raises on a wrong
+    `sides` expectation of an edge request."""
+    b = sc.edge_batch()
+    reqs = b["reqs"]
+
+    def pick(pred):
+        return next(q for q in reqs if pred(q))
+
+    def wrong(q, **want):
+        _raises(lambda: sc.check_edge_intent(dict(q, want=dict(q["want"], **want))))
+
+    q = pick(lambda q: q["kind"].startswith("s_digits: compact -half at 7,"))
+    sc.check_edge_intent(q)
+    wrong(q, digits={"7": -32767, "8": 1})                                # one digit expectation off by one
+    wrong(q, digits={"7": -32768})                                        # the carry above it is not "other digits 0"
+    wrong(q, set="large")
+    wrong(q, r_mixed=1 - q["want"]["r_mixed"])
+    _raises(lambda: sc.check_edge_intent(dict(q, S=q["S"] + 1)))
+    q = pick(lambda q: q["want"].get("value") == "L-1")
+    wrong(q, value="L-2")
+    q = pick(lambda q: q["family"] == "s_canonical" and 2**252 <= q["S"] < L)
+    wrong(q, lt_l=0)
+    wrong(q, ge_2_252=0)
+    _raises(lambda: sc.check_edge_intent(dict(q, S=q["S"] + 2**32 * 0x10000000)))
+    q = pick(lambda q: q["want"].get("q_order") == 1)
+    wrong(q, q_order=2)
+    _raises(lambda: sc.check_edge_intent(dict(q, S=q["S"] ^ 1)))
+    q = pick(lambda q: q["want"].get("q_order") == 4)
+    wrong(q, q_order=8)
+    q = pick(lambda q: q["want"].get("q") == "2sb")
+    _raises(lambda: sc.check_edge_intent(dict(q, R=reqs[0]["R"])))
+    q = pick(lambda q: "a_mixed" in q["want"])
+    _raises(lambda: sc.check_edge_intent(dict(q, A=reqs[0]["A"])))
+    _raises(lambda: sc.check_edge_intent(dict(q, msg=q["msg"][:-1] + bytes([q["msg"][-1] ^ 1]))))   # 8 no longer divides h
+    q = pick(lambda q: q["family"] == "accepted" and q["want"]["set"] == "large")
+    wrong(q, digits={k: v + 1 for k, v in q["want"]["digits"].items()})
+    _raises(lambda: sc.check_edge_intent(dict(q, valid=0)))
+    _raises(lambda: sc.check_edge_intent(dict(reqs[0], valid=1)))
+    _raises(lambda: sc.check_edge_intent(dict(reqs[0], msg=bytes(91))))
+    sc.check_edge_layout(reqs)
+    _raises(lambda: sc.check_edge_layout(reqs[1:] + reqs[:1]))            # slots 62 / 63 and the last request move
+    b_enc = sc.mc.ed_encode(sc.base_mult(1))
+    _raises(lambda: sc.check_edge_layout([reqs[0] if x["A"] == b_enc else x for x in reqs]))               # no key B
+    _raises(lambda: sc.check_edge_layout([reqs[0] if abs(sc.recode_sb(x["S"], "large")[10]) == 2**21 else x
+                                          for x in reqs]))                 # the last entry of table 10 never gathered
+    # a wrong `sides` expectation: the state checker raises
+    n = 65
+    good = sc.prep_state(B, n, "compact", False, False, E)
+    sc.check_prep_state(b, n, good, False)
+    i = next(i for i in range(n) if reqs[i]["family"] == "s_canonical" and reqs[i]["S"] < L)
+    bad = dict(b, reqs=reqs[:i] + [dict(reqs[i], sides=(0, 1, 1))] + reqs[i + 1:])
+    _raises(lambda: sc.check_prep_state(bad, n, good, False))
+    i = next(i for i in range(n) if reqs[i]["want"].get("q_order") == 1)
+    shifted = dict(reqs[i], rtab=sc.multiples(sc.base_mult(1)))             # Q expected to be B, not the identity
+    _raises(lambda: sc.check_prep_state(dict(b, reqs=reqs[:i] + [shifted] + reqs[i + 1:]), n, good, False))
+    lat = sc.lat_phase1_state(B, "rtl", n, "compact", E)
+    sc.check_lat_phase1("rtl", b, n, lat)
+    _raises(lambda: sc.check_lat_phase1("rtl", bad, n, lat))
+
+
 # ---- the latency kernels' families (the latency probes) on the CPU references
 # (hc_stage_latency_phase1 / _walk: references that prove the cases and the
 # checkers, not a build of the quad code, which has none on the CPU)
-KERNELS = ("rtl", "quad")
 
 
 @pytest.mark.parametrize("kernel", KERNELS)
