@@ -2,7 +2,9 @@
 // per-signature algorithm (edv_math.h, edv_verify_core.h) as plain C++ so the
 // CPU test suite can check them against the oracle and Python big integers
 // without a GPU.  Nothing in the product path (libedv.so, the Python shim)
-// loads this library; it is not a fallback.
+// loads this library; it is not a fallback.  fe_sq_floor is built as the prep
+// kernel builds it, with its columns chained (edv_math.h).
+#define EDV_CHAIN_FLOOR 1
 #include <stdint.h>
 #include <string.h>
 #include <vector>
@@ -84,6 +86,7 @@ void hc_fe_mul(const int32_t* f, const int32_t* g, int32_t* h) { from_fe(h, fe_m
 void hc_fe_sq(const int32_t* f, int32_t* h) { from_fe(h, fe_sq(to_fe(f))); }
 void hc_fe_sq_floor(const int32_t* f, int32_t* h) { from_fe(h, fe_sq_floor(to_fe(f))); }
 void hc_fe_sq2(const int32_t* f, int32_t* h) { from_fe(h, fe_sq2(to_fe(f))); }
+void hc_fe_sqn(const int32_t* f, int n, int32_t* h) { from_fe(h, fe_sqn(to_fe(f), n)); }
 void hc_fe_carry32(const int32_t* f, int32_t* h) { from_fe(h, fe_carry32(to_fe(f))); }
 void hc_fe_invert(const int32_t* f, int32_t* h) { from_fe(h, fe_invert(to_fe(f))); }
 void hc_fe_invert_safegcd(const int32_t* f, int32_t* h) { from_fe(h, fe_invert_safegcd(to_fe(f))); }

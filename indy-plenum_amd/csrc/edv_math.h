@@ -164,18 +164,23 @@ EDV_HD void sched_fence() {
 #endif
 }
 
-EDV_HD fe fe_mul(const fe& f, const fe& g) {
-  sched_fence();
-  int32_t g19[10], f2[10];
+// The operands of a product, premultiplied once, and its column sums.  (A
+// struct, not locals of fe_mul: the same sums, but with them the prep kernel
+// allocates at 148 bytes of scratch per lane and as locals at 156.)
+struct fe_mul_cols {
+  int32_t f[10], g[10], g19[10], f2[10], f38_9;
+  EDV_HD fe_mul_cols(const fe& ff, const fe& gg) {
 #pragma unroll
-  for (int i = 0; i < 10; i++) {
-    g19[i] = 19 * g.v[i];
-    f2[i] = (i & 1) ? 2 * f.v[i] : f.v[i];
+    for (int i = 0; i < 10; i++) {
+      f[i] = ff.v[i];
+      g[i] = gg.v[i];
+      g19[i] = 19 * gg.v[i];
+      f2[i] = (i & 1) ? 2 * ff.v[i] : ff.v[i];
+    }
+    f38_9 = 38 * ff.v[9];
   }
-  const int32_t f38_9 = 38 * f.v[9];
-  int64_t h[10];
-#pragma unroll
-  for (int k = 0; k < 10; k++) {
+  // start + column k
+  EDV_HD int64_t col(int k, int64_t start) const {
     int64_t acc = 0;
 #pragma unroll
     for (int i = 0; i < 10; i++) {
@@ -183,12 +188,19 @@ EDV_HD fe fe_mul(const fe& f, const fe& g) {
       // f_9 g_j with j odd wraps with weight 2 * 19: as (38 f_9) g_j, so
       // neither 2 f_9 nor 19 g_1 is needed (13 premultiplied operands, not 14)
       const bool f9w = (i == 9) && (j < 0) && ((j + 10) & 1);
-      const int32_t a = f9w ? f38_9 : ((k & 1) == 0) ? f2[i] : f.v[i];
-      const int32_t b = f9w ? g.v[j + 10] : (j >= 0) ? g.v[j] : g19[j + 10];
-      acc = (i == 0) ? int64_t(a) * int64_t(b) + bias_reg(k) : acc + int64_t(a) * int64_t(b);
+      const int32_t a = f9w ? f38_9 : ((k & 1) == 0) ? f2[i] : f[i];
+      const int32_t b = f9w ? g[j + 10] : (j >= 0) ? g[j] : g19[j + 10];
+      acc = int64_t(a) * int64_t(b) + ((i == 0) ? start : acc);
     }
-    h[k] = acc;
+    return acc;
   }
+};
+EDV_HD fe fe_mul(const fe& f, const fe& g) {
+  sched_fence();
+  const fe_mul_cols cols(f, g);
+  int64_t h[10];
+#pragma unroll
+  for (int k = 0; k < 10; k++) h[k] = cols.col(k, bias_reg(k));
   const fe r = fe_carry64_biased(h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8], h[9]);
   sched_fence();
   return r;
@@ -265,12 +277,75 @@ EDV_HD int32_t carry_floor(int64_t t, int64_t& next) {
   next += t >> W;  // arithmetic shift: floor
   return int32_t(uint32_t(t) & ((1u << W) - 1));
 }
+// x + p in a column that starts from the carry of the column before.  The
+// carry is the deepest value of the column sum, so as plain adds LLVM's
+// reassociation sums the products on their own and adds the carry last: the
+// 64-bit add the chain is there to save.  Reassociation only looks through
+// sums with a single use, so every partial sum gets a second one, an asm that
+// reads it and emits nothing.  (An asm that also writes the sum costs an s_nop
+// before the v_mad_i64_i32 that follows it; an overflow-checked add with its
+// flag unused is folded back to a plain add.)
+EDV_HD int64_t chain_add(int64_t x, int64_t p) {
+  const int64_t r = x + p;
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : : "v"(r));
+#endif
+  return r;
+}
+// start + column k of f^2 (kSqSplit), the products chained onto start in order
+struct fe_sq_colsum {
+  const fe& f;
+  EDV_HD int64_t col(int k, int64_t start) const {
+    int64_t acc = 0;
+    bool first = true;
+#pragma unroll
+    for (int i = 0; i < 10; i++) {
+#pragma unroll
+      for (int j = i; j < 10; j++) {
+        if ((i + j) % 10 != k) continue;
+        const sq_split m = kSqSplit[0][i][j];
+        const int32_t a = f.v[i] * int32_t(m.x), b = f.v[j] * int32_t(m.y);
+        acc = chain_add(first ? start : acc, int64_t(a) * int64_t(b));
+        first = false;
+      }
+    }
+    return acc;
+  }
+};
+// The columns are summed in order 0 .. 9 and column k + 1 STARTS from column
+// k's carry t_k >> W_k, as the addend of its first v_mad_i64_i32: the same
+// integer t_(k+1) as adding the carry to the finished column, hence the same
+// limbs, with nine 64-bit adds fewer (a column is < 2^59 and a carry < 2^34,
+// wherever it enters).  The price is one dependency chain through all 55
+// products.  That pays where other waves fill the gaps, so a translation unit
+// asks for it (EDV_CHAIN_FLOOR 1, as with EDV_SQN_FLOOR): the prep kernel,
+// three waves per SIMD, does (-3 %); the latency kernels, at or below one
+// wave per SIMD, keep the adds.  The rounding chain of fe_mul / fe_sq /
+// fe_sq2 is NOT built this way: chained in pairs (an even column starting at
+// 2^25 + 2^50 carries the next column's bias in), it made the main kernel,
+// one wave per SIMD, 3.7 % slower with 4 % fewer instructions (DESIGN.md
+// section 3).
+#ifndef EDV_CHAIN_FLOOR
+#define EDV_CHAIN_FLOOR 0
+#endif
 EDV_HD fe fe_sq_floor(const fe& f) {
   sched_fence();
+  int32_t o[10];
+  int64_t c9 = 0;
+#if EDV_CHAIN_FLOOR
+  const fe_sq_colsum cols{f};
+  int64_t c = zero_reg();
+#pragma unroll
+  for (int k = 0; k < 10; k++) {
+    const int w = (k & 1) ? 25 : 26;
+    const int64_t t = cols.col(k, c);
+    o[k] = int32_t(uint32_t(t) & ((1u << w) - 1));
+    c = t >> w;  // arithmetic shift: floor
+  }
+  c9 = c;
+#else
   int64_t h[10];
   fe_sq_cols<false, false>(f, h);
-  int64_t c9 = 0;
-  int32_t o[10];
   o[0] = carry_floor<26>(h[0], h[1]);
   o[1] = carry_floor<25>(h[1], h[2]);
   o[2] = carry_floor<26>(h[2], h[3]);
@@ -281,6 +356,7 @@ EDV_HD fe fe_sq_floor(const fe& f) {
   o[7] = carry_floor<25>(h[7], h[8]);
   o[8] = carry_floor<26>(h[8], h[9]);
   o[9] = carry_floor<25>(h[9], c9);
+#endif
   int64_t t0 = int64_t(o[0]) + 19 * c9, t1 = o[1];
   o[0] = carry_floor<26>(t0, t1);
   o[1] = int32_t(t1);

@@ -3,6 +3,9 @@
 // in its own translation unit so it is compiled without the field
 // arithmetic's scheduling fences (see edv_kernels.h).
 #define EDV_NO_SCHED_FENCE 1
+// fe_sq_floor's columns chained through their carries (edv_math.h): this
+// kernel runs three waves per SIMD, which fill the chain's dependency gaps
+#define EDV_CHAIN_FLOOR 1
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

@@ -3,7 +3,10 @@
 // edv_probe_ops.h's probe_lane_op, which calls the header function unchanged;
 // compiled like the batch path's main kernel (edv_verify.hip), with the field
 // arithmetic's scheduling fences.  Straight-line code and loops with fixed
-// bounds only.
+// bounds only.  fe_sq_floor's chained columns are on, as in the prep kernel,
+// the one that runs them: the unchained form is what the latency probes
+// (edv_probe_latency.hip) and every verdict test of that path cover.
+#define EDV_CHAIN_FLOOR 1
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
