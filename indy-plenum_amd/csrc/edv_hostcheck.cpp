@@ -13,6 +13,7 @@
 #include "edv_merkle.h"
 #include "edv_ledger.h"
 #include "edv_tables.h"
+#include "edv_hostplan.h"
 #include "edv_selftest_cases.h"
 #include "edv_probe_ops.h"
 
@@ -510,6 +511,40 @@ void hc_choose_tables(int policy, uint64_t n, int have_compact, int have_large, 
   out3[0] = c.use;
   out3[1] = c.build;
   out3[2] = c.failed ? 1 : 0;
+}
+// the host paths' arithmetic (edv_hostplan.h), as the runtime computes it
+// out: pks, off, msgs, bytes, padded
+void hc_packed_layout(uint64_t n, uint64_t mbytes, uint64_t* out5) {
+  const PackedLayout l = packed_layout(n, mbytes);
+  const uint64_t v[5] = {l.pks, l.off, l.msgs, l.bytes, l.padded};
+  memcpy(out5, v, sizeof v);
+}
+// out: gp, go, span; returns one
+int hc_one_span(uint64_t as, uint64_t ap, uint64_t ao, uint64_t n, uint64_t* out3) {
+  const OneSpan s = one_span(as, ap, ao, n);
+  out3[0] = s.gp;
+  out3[1] = s.go;
+  out3[2] = s.span;
+  return s.one ? 1 : 0;
+}
+uint64_t hc_chunk_capacity(uint64_t need, uint64_t limit) { return chunk_capacity(need, limit); }
+uint64_t hc_pinned_capacity(uint64_t bytes) { return pinned_capacity(bytes); }
+// rb: kSlices + 1 = 9 bounds; returns K
+int hc_field_slices(uint64_t n, int host_slices, int bucketed, uint64_t block, uint64_t* rb) {
+  return field_slices(n, host_slices, bucketed != 0, block, rb);
+}
+// out: Q, pmax, P, nsub
+void hc_sub_split(uint64_t n, uint64_t chunk, uint64_t block, uint64_t* out4) {
+  const SubSplit s = sub_split(n, chunk, block);
+  const uint64_t v[4] = {uint64_t(s.Q), s.pmax, s.P, s.nsub};
+  memcpy(out4, v, sizeof v);
+}
+// out: slots, sigs, pks, acc, dig, msgs, off, slot_off, packed, blob, stage, acc_host, dig_host
+void hc_trim_limits(uint64_t keep, uint64_t chunk, uint64_t* out13) {
+  const TrimLimits t = trim_limits(keep, chunk);
+  const uint64_t v[13] = {t.slots, t.sigs, t.pks,  t.acc,   t.dig,      t.msgs,    t.off,
+                          t.slot_off, t.packed, t.blob, t.stage, t.acc_host, t.dig_host};
+  memcpy(out13, v, sizeof v);
 }
 // the known answers of edv_self_test (edv_selftest_cases.h), as the library holds them
 int hc_selftest_count() { return kSelfTestCases; }

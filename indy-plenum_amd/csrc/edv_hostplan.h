@@ -1,0 +1,99 @@
+// edv_hostplan.h -- the arithmetic of the host paths (edv_runtime.hip): the
+// packed layout of a batch, the single-copy test, slices and sub-batches of a
+// shard, how far buffers grow and what a trim keeps.  Plain C++, no HIP types:
+// libedv_hostcheck.so and tools/ubsan_hostplan.cpp check what the library runs.
+#pragma once
+#include <stdint.h>
+
+namespace edv {
+
+// Message slices of the synchronous field-ordered path (edv_set_host_slices):
+// the hash side of slice k runs while slice k+1 copies.
+constexpr int kSlices = 8;
+constexpr uint64_t kMinSliceReqs = 65536;
+constexpr uint64_t kTrimMsgBytes = 4096;  // message bytes per request of keep_batch a buffer may hold and survive edv_trim
+constexpr uint64_t kReadSlack = 64;       // bytes readable past the last message (the kernels read whole aligned words)
+constexpr uint64_t kSpanGapMax = 4096;    // padding a single-copy span may carry between its three regions
+
+// One block per batch of n requests: signatures (at 0) | keys | offsets |
+// messages; signatures and keys stay 16-byte aligned, offsets 8-byte aligned.
+struct PackedLayout {
+  uint64_t pks, off, msgs;  // byte offsets of the parts
+  uint64_t bytes, padded;   // ... of the end of the messages, and of the read slack behind them
+};
+inline PackedLayout packed_layout(uint64_t n, uint64_t mbytes) {
+  const uint64_t msgs = 96 * n + 8 * (n + 1);
+  return {64 * n, 96 * n, msgs, msgs + mbytes, msgs + mbytes + kReadSlack};
+}
+
+// Signatures, keys and offsets of n requests at host addresses as, ap, ao go
+// to the device in ONE copy of `span` bytes from `as` when they lie in that
+// order without overlap, with little padding, aligned relative to the
+// signatures: the device block then has the keys at gp, the offsets at go.
+// Otherwise gp, go and span are the packed layout's (three copies, one block).
+struct OneSpan {
+  bool one;
+  uint64_t gp, go, span;
+};
+inline OneSpan one_span(uint64_t as, uint64_t ap, uint64_t ao, uint64_t n) {
+  const uint64_t gp = ap - as, go = ao - as, span = go + 8 * (n + 1);
+  if (ap >= as + 64 * n && ao >= ap + 32 * n && span <= 104 * n + 8 + kSpanGapMax && gp % 16 == 0 && go % 8 == 0)
+    return {true, gp, go, span};
+  const PackedLayout l = packed_layout(n, 0);
+  return {false, l.pks, l.off, l.msgs};
+}
+
+// Signatures a chunk state set holds once grown to `need`: powers of two from 4,096, at most `limit` (the chunk).
+inline uint64_t chunk_capacity(uint64_t need, uint64_t limit) {
+  uint64_t c = 4096;
+  while (c < need) c <<= 1;
+  return c <= limit ? c : (limit > need ? limit : need);
+}
+// What a pinned buffer asked for `bytes` is allocated with (headroom: message bytes vary from call to call).
+inline uint64_t pinned_capacity(uint64_t bytes) { return bytes + bytes / 4 + 4096; }
+
+// The field path's K message slices of a shard, slice k = requests [rb[k],
+// rb[k+1]), every bound but the last a multiple of `block`: one per
+// kMinSliceReqs requests (below that a slice's hash side takes a whole wave's
+// latency, so smaller slices only add copy gaps: profiles/r05/trace_sync_s1.json),
+// at most kSlices; host_slices > 0 overrides; a bucketed shard is one slice.
+inline int field_slices(uint64_t n, int host_slices, bool bucketed, uint64_t block, uint64_t rb[kSlices + 1]) {
+  uint64_t K = bucketed ? 1 : (host_slices > 0 ? uint64_t(host_slices) : n / kMinSliceReqs);
+  if (K < 1) K = 1;
+  if (K > uint64_t(kSlices)) K = kSlices;
+  if (K * block > n) K = n / block > 1 ? n / block : 1;
+  for (uint64_t k = 0; k <= K; k++) rb[k] = k == K ? n : (n * k / K) / block * block;
+  return int(K);
+}
+
+// A shard larger than one chunk: nsub sub-batches of P requests alternate over
+// Q streams, stream q on scratch slots [q pmax, (q + 1) pmax); else one sub-batch.
+struct SubSplit {
+  uint64_t Q, pmax, P, nsub;
+};
+inline SubSplit sub_split(uint64_t n, uint64_t chunk, uint64_t block) {
+  const uint64_t Q = (n > chunk && chunk >= 2 * block) ? 2 : 1, pmax = chunk / Q;
+  uint64_t P = ((n + Q - 1) / Q + 63) / 64 * 64;
+  if (P > pmax) P = pmax;
+  return {Q, pmax, P, P ? (n + P - 1) / P : 0};
+}
+
+// What edv_trim keeps: a buffer larger than a batch of `keep` requests with
+// kTrimMsgBytes of message each needs is freed (keep == 0: every buffer).
+struct TrimLimits {
+  uint64_t slots;                      // chunk state sets, in signatures (what such a batch grows a set to)
+  uint64_t sigs, pks, acc, dig;
+  uint64_t msgs, off, slot_off;        // the context's messages and offsets (a window per sub-batch); a slot's offsets
+  uint64_t packed, blob;               // signatures | keys | offsets in one span; ... and the messages
+  uint64_t stage, acc_host, dig_host;  // pinned buffers, with their headroom
+};
+inline TrimLimits trim_limits(uint64_t keep, uint64_t chunk) {
+  const uint64_t k = keep, msgs = k * kTrimMsgBytes + kReadSlack;  // at keep == 0 too: a buffer of the bare slack stays
+  if (!k) return {0, 0, 0, 0, 0, msgs, 0, 0, 0, 0, 0, 0, 0};
+  const uint64_t packed = 104 * k + 8 + kSpanGapMax, blob = packed + msgs;
+  return {chunk_capacity(k < chunk ? k : chunk, chunk), 64 * k, 32 * k, k, 32 * k, msgs,
+          8 * (k + k / (chunk / 2 ? chunk / 2 : 1) + 2), 8 * (k + 1), packed, blob,
+          pinned_capacity(blob), pinned_capacity(k), pinned_capacity(32 * k)};
+}
+
+}  // namespace edv

@@ -18,6 +18,7 @@
 #include <string>
 
 #include "edv_kernels.h"
+#include "edv_hostplan.h"
 #include "edv_launch.h"
 #include "edv_ledger.h"
 #include "edv_merkle.h"
@@ -50,8 +51,7 @@ struct DevBuf {
   uint64_t cap = 0;
   int ensure(uint64_t bytes) {
     if (bytes <= cap) return 0;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
+    release();
     if (hipMalloc(&p, bytes) != hipSuccess) { p = nullptr; return set_err(EDV_E_OOM, "hipMalloc"); }
     cap = bytes;
     return 0;
@@ -69,9 +69,8 @@ struct PinnedBuf {
   uint64_t cap = 0;
   int ensure(uint64_t bytes) {
     if (bytes <= cap) return 0;
-    if (p) (void)hipHostFree(p);
-    p = nullptr; dev = nullptr; cap = 0;
-    bytes = bytes + bytes / 4 + 4096;  // headroom: message bytes vary from call to call
+    release();
+    bytes = pinned_capacity(bytes);  // headroom: message bytes vary from call to call
     if (hipHostMalloc(&p, bytes, hipHostMallocPortable) != hipSuccess) {
       p = nullptr;
       return set_err(EDV_E_OOM, "hipHostMalloc");
@@ -89,16 +88,22 @@ struct PinnedBuf {
   }
 };
 
-// Host path: a shard is walked in sub-batches, round-robin over kQ streams,
-// so the H2D copy of one sub-batch overlaps the kernels of the others and
-// several sub-batches share the chip at once (a 64k batch split 4 ways still
-// fills every SIMD).  Sub-batch stream q uses scratch slots [q*P, (q+1)*P) of
-// the chunk state.
+// Where a host path's n verdicts go (sink_open, sink_d2h, sink_deliver): the
+// kernels write them to `dev`; they reach the page-locked `host` (the caller's
+// buffer if pinned, else the library's) by themselves when zero_copy (`dev` is
+// its device-side address), else by a D2H copy; a pageable `caller` buffer
+// gets them by memcpy once they are in.
+struct VerdictSink {
+  uint8_t *caller = nullptr, *host = nullptr, *dev = nullptr;
+  uint64_t n = 0;
+  bool pinned = false, zero_copy = false;
+};
+
+// The host-path streams.  A shard larger than a chunk alternates its sub-batches
+// over the first two (sub_split), so the H2D copy of one overlaps the kernels
+// of the other; stream q uses scratch slots [q pmax, (q + 1) pmax).  The field
+// path runs on hs[0] and spreads its message slices' hash sides over hs[1..3].
 constexpr int kQ = 4;
-// Message slices of the synchronous field-ordered path (run_shard_fields): the
-// hash side of slice k runs while slice k+1 copies.  edv_set_host_slices.
-constexpr int kSlices = 8;
-constexpr uint64_t kMinSliceReqs = 65536;
 // In-flight batches of the asynchronous host path per device: a Node keeps one
 // per prod in flight, and a pool of nodes in one process (C5) one per node, so
 // eight slots let up to eight callers overlap before a submission has to wait.
@@ -135,9 +140,7 @@ struct ChunkBufs {
   bool fits(uint64_t need) const { return need <= cap; }
   int ensure(uint64_t need, uint64_t limit) {
     if (need <= cap) return 0;
-    uint64_t c = 4096;
-    while (c < need) c <<= 1;
-    if (c > limit) c = limit > need ? limit : need;
+    const uint64_t c = chunk_capacity(need, limit);
     if (atab.ensure(c * kAWords * 4) || rtab.ensure(c * kAWords * 4) || dig.ensure(c * kDigWords * 4) ||
         alive.ensure(3 * c) || perm.ensure(c * 4) || bucket_ctr.ensure(uint64_t(kQ) * 2 * kBuckets * 4)) {
       cap = 0;
@@ -180,9 +183,10 @@ struct DevCtx {
   hipStream_t hs[kQ] = {};
   hipEvent_t hs_staged[kQ] = {};   // pinned slot q may be refilled once its H2D copies are done
   hipEvent_t hs_end[kQ] = {};
-  // split-prep host path (run_shard_split): copies on hcp, part q's prep on hs[q]
+  // the field path: copies on hcp; part_copied: signatures, keys and offsets
+  // are on the device; part_prepped: the bucket permutation is written
   hipStream_t hcp = nullptr;
-  hipEvent_t part_copied[kQ] = {}, part_prepped[kQ] = {};
+  hipEvent_t part_copied = nullptr, part_prepped = nullptr;
   hipEvent_t slice_copied[kSlices] = {}, slice_hashed[kSlices] = {};
   int host_slices = 0;              // 0 = one slice per kMinSliceReqs requests
   // asynchronous host path (edv_verify_batch_async): kAsyncSlots slots used in turn,
@@ -193,10 +197,9 @@ struct DevCtx {
     PinnedBuf stage, acc_host, dig_host;
     hipEvent_t copied = nullptr, done = nullptr;
     int64_t ticket = -1;         // batch held by the slot, -1 = none
-    uint8_t* accept = nullptr;   // the caller's verdict buffer
+    VerdictSink verdicts;        // where the batch's verdicts go (async_complete hands them over)
     uint8_t* digests = nullptr;  // the caller's SHA-256 buffer (null: none asked for)
     uint64_t n = 0;
-    bool acc_pinned = false;     // verdicts DMA'd straight into `accept`
     bool dig_pinned = false;     // digests DMA'd straight into `digests`
     hipStream_t st = nullptr;    // small batches: copies, kernels and D2H all on this stream
     ChunkBufs cb;                // small batches: the slot's own chunk scratch (grown to the batch)
@@ -356,6 +359,32 @@ int device_count_locked() {
   return logical;
 }
 
+// Every stream and every event a context can hold, each list written once, for
+// creation, destruction, drain and quiesce: f(object, lazy), lazy = created on
+// first use by its path (a slot's stream, the pipeline's streams and events,
+// the Merkle scratch's event) and null until then, the others by ctx_init.
+template <class F>
+void for_each_stream(DevCtx& c, F f) {
+  f(c.stream, false);
+  for (hipStream_t& s : c.hs) f(s, false);
+  for (hipStream_t* s : {&c.hcp, &c.hac}) f(*s, false);
+  for (auto& a : c.as) f(a.st, true);
+  for (hipStream_t* s : {&c.sp, &c.sm}) f(*s, true);
+}
+template <class F>
+void for_each_event(DevCtx& c, F f) {
+  for (auto* set : {&c.hs_staged, &c.hs_end})
+    for (hipEvent_t& e : *set) f(e, false);
+  for (auto* set : {&c.slice_copied, &c.slice_hashed})
+    for (hipEvent_t& e : *set) f(e, false);
+  for (auto& a : c.as)
+    for (hipEvent_t* e : {&a.copied, &a.done}) f(*e, false);
+  for (hipEvent_t* e : {&c.part_copied, &c.part_prepped, &c.st_done}) f(*e, false);
+  for (auto* set : {&c.prep_done, &c.main_done, &c.perm_done})
+    for (hipEvent_t& e : *set) f(e, true);
+  for (hipEvent_t* e : {&c.inputs_ready, &c.mk_done}) f(*e, true);
+}
+
 // Idempotent: a failure part-way leaves what was created in place and the next
 // call resumes from there (no second stream or table per retry).
 int ctx_init(DevCtx& c) {
@@ -364,25 +393,15 @@ int ctx_init(DevCtx& c) {
   hipDeviceProp_t prop;
   HIPOK(hipGetDeviceProperties(&prop, c.phys), "hipGetDeviceProperties");
   if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) return set_err(EDV_E_NODEV, "device is not gfx950");
-  if (!c.stream) HIPOK(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking), "hipStreamCreate");
-  for (int q = 0; q < kQ; q++) {
-    if (!c.hs[q]) HIPOK(hipStreamCreateWithFlags(&c.hs[q], hipStreamNonBlocking), "hipStreamCreate");
-    if (!c.hs_staged[q]) HIPOK(hipEventCreateWithFlags(&c.hs_staged[q], hipEventDisableTiming), "event");
-    if (!c.hs_end[q]) HIPOK(hipEventCreateWithFlags(&c.hs_end[q], hipEventDisableTiming), "event");
-    if (!c.part_copied[q]) HIPOK(hipEventCreateWithFlags(&c.part_copied[q], hipEventDisableTiming), "event");
-    if (!c.part_prepped[q]) HIPOK(hipEventCreateWithFlags(&c.part_prepped[q], hipEventDisableTiming), "event");
-  }
-  for (int k = 0; k < kSlices; k++) {
-    if (!c.slice_copied[k]) HIPOK(hipEventCreateWithFlags(&c.slice_copied[k], hipEventDisableTiming), "event");
-    if (!c.slice_hashed[k]) HIPOK(hipEventCreateWithFlags(&c.slice_hashed[k], hipEventDisableTiming), "event");
-  }
-  if (!c.hcp) HIPOK(hipStreamCreateWithFlags(&c.hcp, hipStreamNonBlocking), "hipStreamCreate");
-  if (!c.hac) HIPOK(hipStreamCreateWithFlags(&c.hac, hipStreamNonBlocking), "hipStreamCreate");
-  for (auto& s : c.as) {
-    if (!s.copied) HIPOK(hipEventCreateWithFlags(&s.copied, hipEventDisableTiming), "event");
-    if (!s.done) HIPOK(hipEventCreateWithFlags(&s.done, hipEventDisableTiming), "event");
-  }
-  if (!c.st_done) HIPOK(hipEventCreateWithFlags(&c.st_done, hipEventDisableTiming), "event");
+  hipError_t made = hipSuccess;
+  for_each_stream(c, [&](hipStream_t& s, bool lazy) {
+    if (made == hipSuccess && !lazy && !s) made = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+  });
+  HIPOK(made, "hipStreamCreate");
+  for_each_event(c, [&](hipEvent_t& ev, bool lazy) {
+    if (made == hipSuccess && !lazy && !ev) made = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+  });
+  HIPOK(made, "event");
   if (const char* e = c.env_read ? nullptr : getenv("EDV_CHUNK")) {
     const uint64_t v = strtoull(e, nullptr, 10);
     if (v >= kBlock && v <= (uint64_t(1) << 24)) c.chunk = (v / kBlock) * kBlock;
@@ -579,9 +598,21 @@ int launch_quad(DevCtx& c, DevBuf& qtab, const uint8_t* d_sigs, const uint8_t* d
   return 0;
 }
 
+// The chunk walk: requests [0, n) of va in chunks of `step` on stream s, per chunk [length buckets (ctr: this
+// stream's histogram + cursors),] prep kernel, main kernel.  The caller orders the scratch (st_done).
+int walk_chunks(uint32_t* ctr, VerifyArgs va, bool bucket, uint64_t n, uint64_t step, hipStream_t s) {
+  int err;
+  for (uint64_t base = 0; base < n; base += step) {
+    va.base = base;
+    va.n = (n - base) < step ? (n - base) : step;
+    if ((err = launch_prep(ctr, va, va.off, bucket, s)) || (err = launch_main(va, s))) return err;
+  }
+  return 0;
+}
+
 // Ordinary device path: launch on stream s; caller holds c.mu.  The batch is
-// walked in chunks of c.chunk signatures: [length buckets,] prep kernel, main
-// kernel, all in stream order, after every earlier user of the scratch.
+// walked in chunks of c.chunk signatures (walk_chunks), after every earlier
+// user of the scratch.
 int launch(DevCtx& c, const uint8_t* d_sigs, const uint8_t* d_pks, const uint8_t* d_msgs, const uint64_t* d_off,
            uint64_t msg_base, uint64_t n, uint8_t* d_accept, hipStream_t s, uint32_t flags) {
   if (n == 0) return 0;
@@ -595,36 +626,24 @@ int launch(DevCtx& c, const uint8_t* d_sigs, const uint8_t* d_pks, const uint8_t
   }
   if ((err = grow_state(c, n))) return err;
   HIPOK(hipStreamWaitEvent(s, c.st_done, 0), "wait scratch");
-  VerifyArgs va = make_args(c, c.st, d_sigs, d_pks, d_msgs, d_off, msg_base, d_accept, bucket, 0, n);
+  const VerifyArgs va = make_args(c, c.st, d_sigs, d_pks, d_msgs, d_off, msg_base, d_accept, bucket, 0, n);
   if (!va.btab) return no_tables(c);
-  for (uint64_t base = 0; base < n; base += c.chunk) {
-    va.base = base;
-    va.n = (n - base) < c.chunk ? (n - base) : c.chunk;
-    if ((err = launch_prep(bucket_ctr(c.st, 0), va, d_off, bucket, s)) || (err = launch_main(va, s))) return err;
-  }
+  if ((err = walk_chunks(bucket_ctr(c.st, 0), va, bucket, n, c.chunk, s))) return err;
   HIPOK(hipEventRecord(c.st_done, s), "record scratch");
   return 0;
 }
 
-// A small asynchronous batch on its slot's own scratch (cb, grown to the
-// batch by the caller once the slot's previous batch is complete) and stream:
-// no ordering against the shared scratch, so batches of different slots run
-// concurrently.  Chunks of at most c.chunk, as launch() walks them.
+// A small asynchronous batch on its slot's own scratch (cb, grown to the batch
+// by the caller once the slot's previous batch is complete) and stream: not
+// ordered against the shared scratch, so batches of different slots run side by side.
 int launch_own(DevCtx& c, ChunkBufs& cb, const uint8_t* d_sigs, const uint8_t* d_pks, const uint8_t* d_msgs,
                const uint64_t* d_off, uint64_t msg_base, uint64_t n, uint8_t* d_accept, hipStream_t s,
                uint32_t flags) {
   if (n == 0) return 0;
   const bool bucket = bucketing_enabled(c, flags);
-  VerifyArgs va = make_args(c, cb, d_sigs, d_pks, d_msgs, d_off, msg_base, d_accept, bucket, 0, n);
+  const VerifyArgs va = make_args(c, cb, d_sigs, d_pks, d_msgs, d_off, msg_base, d_accept, bucket, 0, n);
   if (!va.btab) return no_tables(c);
-  const uint64_t step = c.chunk < cb.cap ? c.chunk : cb.cap;
-  int err;
-  for (uint64_t base = 0; base < n; base += step) {
-    va.base = base;
-    va.n = (n - base) < step ? (n - base) : step;
-    if ((err = launch_prep(bucket_ctr(cb, 0), va, d_off, bucket, s)) || (err = launch_main(va, s))) return err;
-  }
-  return 0;
+  return walk_chunks(bucket_ctr(cb, 0), va, bucket, n, c.chunk < cb.cap ? c.chunk : cb.cap, s);
 }
 
 int pipe_init(DevCtx& c) {
@@ -705,20 +724,18 @@ int launch_pipelined(DevCtx& c, const uint8_t* d_sigs, const uint8_t* d_pks, con
 }
 
 // Drain every stream of the context (before scratch is reallocated).
+// The scratch's users on caller streams are waited for through st_done and
+// mk_done; asynchronous batches stay pending until edv_wait_async.  Returns
+// the first error (nothing after it is waited for).
 int drain(DevCtx& c) {
-  HIPOK(hipStreamSynchronize(c.stream), "stream sync");
+  hipError_t e = hipSuccess;
+  for_each_stream(c, [&](hipStream_t& s, bool) {
+    if (e == hipSuccess && s) e = hipStreamSynchronize(s);
+  });
+  HIPOK(e, "stream sync");
   HIPOK(hipEventSynchronize(c.st_done), "scratch sync");
   if (c.mk_done) HIPOK(hipEventSynchronize(c.mk_done), "merkle scratch sync");
-  for (int q = 0; q < kQ; q++) HIPOK(hipStreamSynchronize(c.hs[q]), "stream sync");
-  if (c.hcp) HIPOK(hipStreamSynchronize(c.hcp), "stream sync");
-  if (c.hac) HIPOK(hipStreamSynchronize(c.hac), "stream sync");  // async batches stay pending until edv_wait_async
-  for (auto& s : c.as)
-    if (s.st) HIPOK(hipStreamSynchronize(s.st), "stream sync");
-  if (c.pipe_ready) {
-    HIPOK(hipStreamSynchronize(c.sp), "pipeline sync");
-    HIPOK(hipStreamSynchronize(c.sm), "pipeline sync");
-    c.pending[0] = c.pending[1] = false;
-  }
+  if (c.pipe_ready) c.pending[0] = c.pending[1] = false;
   return 0;
 }
 
@@ -726,11 +743,9 @@ int drain(DevCtx& c) {
 // queued on the context's streams (copies may still read the caller's pinned
 // buffers), so no DMA touches them after the error is returned.
 void quiesce(DevCtx& c) {
-  hipStream_t ss[] = {c.stream, c.hcp, c.hac, c.sp, c.sm};
-  for (hipStream_t x : ss)
-    if (x) (void)hipStreamSynchronize(x);
-  for (int q = 0; q < kQ; q++)
-    if (c.hs[q]) (void)hipStreamSynchronize(c.hs[q]);
+  for_each_stream(c, [](hipStream_t& s, bool) {
+    if (s) (void)hipStreamSynchronize(s);
+  });
   (void)hipGetLastError();
 }
 
@@ -743,6 +758,38 @@ bool is_pinned(const void* p) {
     return false;
   }
   return attr.type == hipMemoryTypeHost;
+}
+
+// ---- the verdict sink for n verdicts owed to `accept`.  Its host side: the
+// caller's buffer if page-locked, else `own`, the path's pinned buffer.
+int sink_host(VerdictSink& v, uint8_t* accept, uint64_t n, PinnedBuf& own) {
+  v = VerdictSink{accept, nullptr, nullptr, n, is_pinned(accept), false};
+  if (!v.pinned && own.ensure(n)) return EDV_E_OOM;
+  v.host = v.pinned ? accept : static_cast<uint8_t*>(own.p);
+  return 0;
+}
+// ... and the address the kernels write: the host side's own (cached for
+// `own`, looked up for a page-locked `accept`), else `fallback`, ensured only then
+int sink_open(VerdictSink& v, uint8_t* accept, uint64_t n, PinnedBuf& own, DevBuf& fallback) {
+  if (sink_host(v, accept, n, own)) return EDV_E_OOM;
+  void* zc = v.pinned ? nullptr : own.dev;
+  if (v.pinned && (hipHostGetDevicePointer(&zc, accept, 0) != hipSuccess || !zc)) {
+    (void)hipGetLastError();
+    zc = nullptr;
+  }
+  if (!zc && fallback.ensure(n)) return EDV_E_OOM;
+  v.zero_copy = zc != nullptr;
+  v.dev = static_cast<uint8_t*>(zc ? zc : fallback.p);
+  return 0;
+}
+// The D2H of the verdicts on stream s, behind the kernels, when they did not write the host memory themselves
+int sink_d2h(const VerdictSink& v, hipStream_t s) {
+  if (!v.zero_copy) HIPOK(hipMemcpyAsync(v.host, v.dev, v.n, hipMemcpyDeviceToHost, s), "d2h accept");
+  return 0;
+}
+// After the sync: a pageable caller buffer gets its verdicts
+void sink_deliver(const VerdictSink& v) {
+  if (!v.pinned) memcpy(v.caller, v.host, v.n);
 }
 
 struct Seg {
@@ -784,20 +831,61 @@ void par_copy(const std::vector<Seg>& segs) {
   for (auto& x : th) x.join();
 }
 
-// One pinned block per batch: signatures | keys | offsets | messages (+ 64
-// bytes of read slack), copied to the device in ONE DMA (each separate copy
-// costs the DMA engine a gap, trace_sync); signatures and keys stay 16-byte
-// aligned, offsets 8-byte aligned.
-uint64_t quad_pack_bytes(uint64_t n, uint64_t mbytes) { return 96 * n + 8 * (n + 1) + mbytes + 64; }
-void quad_pack(uint8_t* dst, const uint8_t* sigs, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off,
-               uint64_t lo, uint64_t hi) {
-  const uint64_t n = hi - lo, mbase = off[lo], mbytes = off[hi] - mbase;
-  par_copy({{dst, sigs + 64 * lo, 64 * n},
-            {dst + 64 * n, pks + 32 * lo, 32 * n},
-            {dst + 96 * n, reinterpret_cast<const uint8_t*>(off + lo), 8 * (n + 1)},
-            {dst + 96 * n + 8 * (n + 1), mbytes ? msgs + mbase : nullptr, mbytes}});
-  memset(dst + 96 * n + 8 * (n + 1) + mbytes, 0, 64);
+// ---- the input stager: requests [lo, hi) of a caller's batch onto the device.
+// Where the four parts are read from: the caller's memory, or the pinned
+// staging once stage_inputs has packed them there.  The offsets stay absolute
+// (msg_base = mbase).
+struct HostIn {
+  const uint8_t *sigs, *pks, *off, *msgs;  // of request lo
+  uint64_t n, mbase, mbytes;
+};
+HostIn host_in(const uint8_t* sigs, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off, uint64_t lo,
+               uint64_t hi) {
+  return {sigs + 64 * lo, pks + 32 * lo,    reinterpret_cast<const uint8_t*>(off + lo), msgs + off[lo],
+          hi - lo,        off[lo],          off[hi] - off[lo]};
 }
+// Page-locked inputs (the native authenticator's arena, edv_host_alloc) are
+// DMA'd straight from the caller's memory: no host copy on the Node's thread.
+bool inputs_pinned(const HostIn& h) {
+  return is_pinned(h.sigs) && is_pinned(h.pks) && is_pinned(h.off) && (h.mbytes == 0 || is_pinned(h.msgs));
+}
+// Pageable inputs are packed into pinned staging (packed_layout, the read
+// slack zeroed), where h reads them afterwards; without the messages, their
+// place is left for the caller to fill (stage_and_send) and h.msgs stays the
+// caller's.  The staging's previous user is done (the caller's to know).
+int stage_inputs(PinnedBuf& stage, HostIn& h, bool with_msgs) {
+  const PackedLayout l = packed_layout(h.n, h.mbytes);
+  if (stage.ensure(l.padded)) return EDV_E_OOM;
+  uint8_t* p = static_cast<uint8_t*>(stage.p);
+  par_copy({{p, h.sigs, 64 * h.n}, {p + l.pks, h.pks, 32 * h.n}, {p + l.off, h.off, 8 * (h.n + 1)},
+            {p + l.msgs, h.msgs, with_msgs ? h.mbytes : 0}});
+  memset(p + l.bytes, 0, kReadSlack);
+  h = {p, p + l.pks, p + l.off, with_msgs ? p + l.msgs : h.msgs, h.n, h.mbase, h.mbytes};
+  return 0;
+}
+// Do h's signatures, keys and offsets go in one copy?  (Once staged, or packed by the caller into one pinned buffer.)
+OneSpan input_span(const HostIn& h) {
+  return one_span(reinterpret_cast<uintptr_t>(h.sigs), reinterpret_cast<uintptr_t>(h.pks),
+                  reinterpret_cast<uintptr_t>(h.off), h.n);
+}
+// h to the device on stream s.  The fixed part (signatures, keys, offsets): ONE
+// copy of `span` bytes to d_sigs, a block laid out as the host region
+// (input_span), when `one`, else three; each separate copy costs the DMA engine
+// a gap (~12 us, trace_sync).  Then the messages in one copy, unless d_msgs is
+// null: the field path sends them in slices.
+int upload(const HostIn& h, bool one, uint64_t span, void* d_sigs, void* d_pks, void* d_off, void* d_msgs,
+           hipStream_t s) {
+  if (one) {
+    HIPOK(hipMemcpyAsync(d_sigs, h.sigs, span, hipMemcpyHostToDevice, s), "h2d sigs+pks+off");
+  } else {
+    HIPOK(hipMemcpyAsync(d_sigs, h.sigs, 64 * h.n, hipMemcpyHostToDevice, s), "h2d sigs");
+    HIPOK(hipMemcpyAsync(d_pks, h.pks, 32 * h.n, hipMemcpyHostToDevice, s), "h2d pks");
+    HIPOK(hipMemcpyAsync(d_off, h.off, 8 * (h.n + 1), hipMemcpyHostToDevice, s), "h2d off");
+  }
+  if (d_msgs && h.mbytes) HIPOK(hipMemcpyAsync(d_msgs, h.msgs, h.mbytes, hipMemcpyHostToDevice, s), "h2d msgs");
+  return 0;
+}
+
 // Pageable inputs of a latency-path batch are packed into page-locked staging
 // anyway; the quad kernel then reads them from there over PCIe (its phase 1
 // reads each input once, at its start) instead of waiting for a DMA of them:
@@ -809,57 +897,39 @@ bool quad_zero_copy() {
   }();
   return on;
 }
-// Device pointers of a latency-path batch
-struct QuadIn {
+// Device pointers of a batch's inputs
+struct DevIn {
   const uint8_t *sigs, *pks, *msgs;
   const uint64_t* off;
 };
-// Requests [lo, hi) into device buffer `blob` on stream s for the quad kernel.
-// Pinned inputs (the native authenticator's page-locked arena, edv_host_alloc)
-// are DMA'd straight from the caller's memory -- signatures, keys and offsets
-// in one copy when they lie in one host region in that order, then the
-// messages: no host copy on the Node's thread; pageable inputs are packed into
-// the pinned `stage` (quad_pack) and copied in one DMA.
-int quad_upload(DevBuf& blob, PinnedBuf& stage, const uint8_t* sigs, const uint8_t* pks, const uint8_t* msgs,
-                const uint64_t* off, uint64_t lo, uint64_t hi, hipStream_t s, QuadIn* d) {
-  const uint64_t n = hi - lo, mbase = off[lo], mbytes = off[hi] - mbase;
-  const uint8_t *src_s = sigs + 64 * lo, *src_p = pks + 32 * lo, *src_m = msgs + mbase;
-  const uint8_t* src_o = reinterpret_cast<const uint8_t*>(off + lo);
-  const bool pinned = is_pinned(src_s) && is_pinned(src_p) && is_pinned(src_o) && (mbytes == 0 || is_pinned(src_m));
-  if (!pinned) {
-    const uint64_t bytes = quad_pack_bytes(n, mbytes);
-    if (stage.ensure(bytes)) return EDV_E_OOM;
-    quad_pack(static_cast<uint8_t*>(stage.p), sigs, pks, msgs, off, lo, hi);
-    if (quad_zero_copy() && stage.dev) {
-      uint8_t* b = static_cast<uint8_t*>(stage.dev);  // read in place (the staging's previous user is done)
-      *d = {b, b + 64 * n, b + 96 * n + 8 * (n + 1), reinterpret_cast<const uint64_t*>(b + 96 * n)};
-      return 0;
+// ... in a block at b with the keys at gp, the offsets at go, the messages at gm
+DevIn dev_in_at(const void* b, uint64_t gp, uint64_t go, uint64_t gm) {
+  const uint8_t* p = static_cast<const uint8_t*>(b);
+  return {p, p + gp, p + gm, reinterpret_cast<const uint64_t*>(p + go)};
+}
+// Inputs h of a latency-path batch for the quad kernel, on stream s: pageable
+// ones are packed into the pinned `stage` and read there by the kernel, or
+// (EDV_QUAD_ZERO_COPY=0) copied from there in ONE DMA; page-locked ones go
+// into device buffer `blob`, the fixed part in one copy when it lies in one region.
+int quad_upload(DevBuf& blob, PinnedBuf& stage, HostIn h, hipStream_t s, DevIn* d) {
+  int err;
+  if (!inputs_pinned(h)) {
+    if ((err = stage_inputs(stage, h, true))) return err;
+    const PackedLayout l = packed_layout(h.n, h.mbytes);
+    const bool in_place = quad_zero_copy() && stage.dev;  // the staging's previous user is done
+    if (!in_place) {  // the whole packed block, messages and slack included, in ONE copy
+      if (blob.ensure(l.padded)) return EDV_E_OOM;
+      HIPOK(hipMemcpyAsync(blob.p, stage.p, l.padded, hipMemcpyHostToDevice, s), "h2d packed");
     }
-    if (blob.ensure(bytes)) return EDV_E_OOM;
-    HIPOK(hipMemcpyAsync(blob.p, stage.p, bytes, hipMemcpyHostToDevice, s), "h2d packed");
-    uint8_t* b = static_cast<uint8_t*>(blob.p);
-    *d = {b, b + 64 * n, b + 96 * n + 8 * (n + 1), reinterpret_cast<const uint64_t*>(b + 96 * n)};
+    *d = dev_in_at(in_place ? stage.dev : blob.p, l.pks, l.off, l.msgs);
     return 0;
   }
-  const uintptr_t as = reinterpret_cast<uintptr_t>(src_s), ap = reinterpret_cast<uintptr_t>(src_p),
-                  ao = reinterpret_cast<uintptr_t>(src_o);
-  const bool one = ap >= as + 64 * n && ao >= ap + 32 * n && ao + 8 * (n + 1) - as <= 104 * n + 8 + 4096 &&
-                   (ap - as) % 16 == 0 && (ao - as) % 8 == 0;
-  const uint64_t span = one ? ao + 8 * (n + 1) - as : 96 * n + 8 * (n + 1);
-  const uint64_t moff = (span + 15) / 16 * 16;
-  if (blob.ensure(moff + mbytes + 64)) return EDV_E_OOM;
+  const OneSpan sp = input_span(h);
+  const uint64_t moff = (sp.span + 15) / 16 * 16;
+  if (blob.ensure(moff + h.mbytes + kReadSlack)) return EDV_E_OOM;
   uint8_t* b = static_cast<uint8_t*>(blob.p);
-  if (one) {
-    HIPOK(hipMemcpyAsync(b, src_s, span, hipMemcpyHostToDevice, s), "h2d sigs+pks+off");
-    *d = {b, b + (ap - as), b + moff, reinterpret_cast<const uint64_t*>(b + (ao - as))};
-  } else {
-    HIPOK(hipMemcpyAsync(b, src_s, 64 * n, hipMemcpyHostToDevice, s), "h2d sigs");
-    HIPOK(hipMemcpyAsync(b + 64 * n, src_p, 32 * n, hipMemcpyHostToDevice, s), "h2d pks");
-    HIPOK(hipMemcpyAsync(b + 96 * n, src_o, 8 * (n + 1), hipMemcpyHostToDevice, s), "h2d off");
-    *d = {b, b + 64 * n, b + moff, reinterpret_cast<const uint64_t*>(b + 96 * n)};
-  }
-  if (mbytes) HIPOK(hipMemcpyAsync(b + moff, src_m, mbytes, hipMemcpyHostToDevice, s), "h2d msgs");
-  return 0;
+  *d = dev_in_at(b, sp.gp, sp.go, moff);
+  return upload(h, sp.one, sp.span, b, b + sp.gp, b + sp.go, b + moff, s);
 }
 // memcpy of src[0, bounds[K]) into pinned staging over copy_threads() threads,
 // part by part (part k = [bounds[k], bounds[k+1])), with part k's DMA to the
@@ -957,11 +1027,15 @@ EDV_HOST_CLONES OffScan scan_offsets(const uint64_t* off, uint64_t lo,
 // SHA-512 block count; -1 = not checked yet: the check runs here, on the host,
 // while the first copy (whose size depends on n only) is already on its way,
 // and a failed check returns EDV_E_ARG before anything reads the offsets.
-int run_shard_fields(DevCtx& c, const uint8_t* sigs, const uint8_t* pks, const uint8_t* msgs, const uint64_t* off,
-                     uint64_t lo, uint64_t hi, bool pinned, int uniform, uint8_t* d_sigs, uint8_t* d_pks,
-                     uint8_t* d_msgs, uint64_t* d_off, uint8_t* d_acc, uint8_t* h_acc) {
-  const uint64_t n = hi - lo, mbase = off[lo], mbytes = off[hi] - mbase;
+// h: the shard's inputs (pinned: page-locked, so copied from where they are);
+// the device buffers c.sigs, pks, msgs, off and acc are the caller's to ensure.
+int run_shard_fields(DevCtx& c, HostIn h, const uint64_t* off, uint64_t lo, uint64_t hi, bool pinned, int uniform,
+                     uint8_t* accept) {
+  const uint64_t n = h.n, mbase = h.mbase, mbytes = h.mbytes;
   const hipStream_t cp = c.hcp, s0 = c.hs[0];
+  uint8_t *d_sigs = static_cast<uint8_t*>(c.sigs.p), *d_pks = static_cast<uint8_t*>(c.pks.p),
+          *d_msgs = static_cast<uint8_t*>(c.msgs.p);
+  uint64_t* d_off = static_cast<uint64_t*>(c.off.p);
   int err;
   if ((err = grow_state(c, n))) return err;
   // the scratch's previous users (any stream) finish before the kernels write it,
@@ -972,35 +1046,23 @@ int run_shard_fields(DevCtx& c, const uint8_t* sigs, const uint8_t* pks, const u
     HIPOK(hipStreamWaitEvent(cp, c.st_done, 0), "wait scratch");
     for (int q = 0; q < kQ; q++) HIPOK(hipStreamWaitEvent(c.hs[q], c.st_done, 0), "wait scratch");
   }
-  const uint8_t *src_s = sigs + 64 * lo, *src_p = pks + 32 * lo, *src_m = msgs + mbase;
-  const uint8_t* src_o = reinterpret_cast<const uint8_t*>(off + lo);
+  const uint8_t* src_m = h.msgs;  // the caller's: staged slice by slice below when pageable
   PinnedBuf& sl = c.stage[0];
   if (!pinned) {
     HIPOK(hipEventSynchronize(c.hs_staged[0]), "stage wait");  // the slot's previous H2D is done
-    if (sl.ensure(n * 96 + (n + 1) * 8 + mbytes)) return EDV_E_OOM;
-    uint8_t* p = static_cast<uint8_t*>(sl.p);
-    par_copy({{p, src_s, 64 * n}, {p + 64 * n, src_p, 32 * n}, {p + 96 * n, src_o, 8 * (n + 1)}});
-    src_s = p; src_p = p + 64 * n; src_o = p + 96 * n;
+    if ((err = stage_inputs(sl, h, false))) return err;
   }
-  // Signatures, keys and offsets that lie in one host region in that order
-  // (always so once staged; so for a caller that packs a batch into one
-  // pinned buffer) go in ONE copy into a device block of the same layout: each
-  // separate copy costs the DMA engine a gap (~12 us each, trace_sync).
-  const uintptr_t as = reinterpret_cast<uintptr_t>(src_s), ap = reinterpret_cast<uintptr_t>(src_p),
-                  ao = reinterpret_cast<uintptr_t>(src_o);
-  const uint64_t gp = ap - as, go = ao - as, span = go + 8 * (n + 1);
-  if (ap >= as + 64 * n && ao >= ap + 32 * n && span <= 104 * n + 8 + 4096 && gp % 16 == 0 && go % 8 == 0) {
-    if (c.fblob.ensure(span)) return EDV_E_OOM;
-    uint8_t* blob = static_cast<uint8_t*>(c.fblob.p);
-    d_sigs = blob;
-    d_pks = blob + gp;
-    d_off = reinterpret_cast<uint64_t*>(blob + go);
-    HIPOK(hipMemcpyAsync(blob, src_s, span, hipMemcpyHostToDevice, cp), "h2d sigs+pks+off");
-  } else {
-    HIPOK(hipMemcpyAsync(d_sigs, src_s, n * 64, hipMemcpyHostToDevice, cp), "h2d sigs");
-    HIPOK(hipMemcpyAsync(d_pks, src_p, n * 32, hipMemcpyHostToDevice, cp), "h2d pks");
-    HIPOK(hipMemcpyAsync(d_off, src_o, (n + 1) * 8, hipMemcpyHostToDevice, cp), "h2d off");
+  // The fixed part in ONE copy, into a device block of the host region's
+  // layout, when it lies in one region (input_span); else into the three buffers.
+  const OneSpan sp = input_span(h);
+  if (sp.one) {
+    if (c.fblob.ensure(sp.span)) return EDV_E_OOM;
+    d_sigs = static_cast<uint8_t*>(c.fblob.p);
+    d_pks = d_sigs + sp.gp;
+    d_off = reinterpret_cast<uint64_t*>(d_sigs + sp.go);
   }
+  // queued before the offsets scan below: its size depends on n only
+  if ((err = upload(h, sp.one, sp.span, d_sigs, d_pks, d_off, nullptr, cp))) return err;
   if (uniform < 0) {
     const OffScan sc = scan_offsets(off, lo, hi);
     if (!sc.ok) {
@@ -1010,42 +1072,33 @@ int run_shard_fields(DevCtx& c, const uint8_t* sigs, const uint8_t* pks, const u
     uniform = sc.uniform ? 1 : 0;
   }
   const bool bucket = bucketing_enabled(c, uniform ? EDV_FLAG_UNIFORM_LENGTH : EDV_FLAG_BUCKETS);
-  // one slice per 65,536 requests (a slice's hash side takes a whole wave's
-  // latency at any size below that, so smaller slices only add copy gaps:
-  // profiles/r05/trace_sync_s1.json), at most kSlices; edv_set_host_slices
-  // overrides; a bucketed shard is one slice
-  int K = bucket ? 1 : (c.host_slices ? c.host_slices : int(n / kMinSliceReqs));
-  if (K < 1) K = 1;
-  if (K > kSlices) K = kSlices;
-  if (uint64_t(K) * kBlock > n) K = int(n / kBlock) > 1 ? int(n / kBlock) : 1;
+  // the message slices (field_slices, edv_hostplan.h): one per 65,536 requests,
+  // edv_set_host_slices overrides; a bucketed shard is one slice
   uint64_t rb[kSlices + 1], mb[kSlices + 1];  // request / message-byte bounds of the slices (shard-relative)
-  for (int k = 0; k <= K; k++) {
-    rb[k] = k == K ? n : (n * k / K) / kBlock * kBlock;
-    mb[k] = off[lo + rb[k]] - mbase;
-  }
-  HIPOK(hipEventRecord(c.part_copied[0], cp), "record");
+  const int K = field_slices(n, c.host_slices, bucket, kBlock, rb);
+  for (int k = 0; k <= K; k++) mb[k] = off[lo + rb[k]] - mbase;
+  HIPOK(hipEventRecord(c.part_copied, cp), "record");
   // The kernels write the verdicts straight into the page-locked host buffer
   // (one 64-byte PCIe write per wave), so no D2H copy and its launch gap follow
   // the main kernel (C2 pinned 1.075 -> 1.046 ms, with the in-stream hash side
   // below 1.033-1.048 ms: profiles/r05/ab_sync_s4.jsonl).
-  void* zc = nullptr;
-  if (hipHostGetDevicePointer(&zc, h_acc, 0) == hipSuccess && zc) d_acc = static_cast<uint8_t*>(zc);
-  else (void)hipGetLastError();
-  const bool zc_acc = zc != nullptr;
+  VerdictSink v;
+  if ((err = sink_open(v, accept, n, c.acc_host, c.acc))) return err;
+  uint8_t* const d_acc = v.dev;
   // the point sides first: they need only what has just been queued
   VerifyArgs va = make_args(c, c.st, d_sigs, d_pks, d_msgs, d_off, mbase, d_acc, bucket, 0, n);
   if (!va.btab) return no_tables(c);
   va.n = n;
-  HIPOK(hipStreamWaitEvent(s0, c.part_copied[0], 0), "wait copy");
+  HIPOK(hipStreamWaitEvent(s0, c.part_copied, 0), "wait copy");
   if (bucket && (err = launch_buckets(bucket_ctr(c.st, 0), va, d_off, s0))) return err;
-  HIPOK(hipEventRecord(c.part_prepped[0], s0), "record");  // the bucket permutation is written
+  HIPOK(hipEventRecord(c.part_prepped, s0), "record");  // the bucket permutation is written
   VerifyArgs vp = va;
   vp.side0 = 1;
   vp.nsides = 2;
   if ((err = launch_prep_sides(vp, s0))) return err;
   // then the messages, slice by slice (staged in the same slices when pageable)
   if (!pinned) {
-    uint8_t* pm = static_cast<uint8_t*>(sl.p) + 96 * n + 8 * (n + 1);
+    uint8_t* pm = static_cast<uint8_t*>(sl.p) + packed_layout(n, mbytes).msgs;
     if (mbytes && (err = stage_and_send(d_msgs, pm, src_m, mb, K, cp, c.slice_copied))) return err;
     if (!mbytes)
       for (int k = 0; k < K; k++) HIPOK(hipEventRecord(c.slice_copied[k], cp), "record");
@@ -1070,17 +1123,17 @@ int run_shard_fields(DevCtx& c, const uint8_t* sigs, const uint8_t* pks, const u
     vh.side0 = 0;
     vh.nsides = 1;
     HIPOK(hipStreamWaitEvent(hk, c.slice_copied[k], 0), "wait copy");
-    if (bucket) HIPOK(hipStreamWaitEvent(hk, c.part_prepped[0], 0), "wait buckets");
+    if (bucket) HIPOK(hipStreamWaitEvent(hk, c.part_prepped, 0), "wait buckets");
     if ((err = launch_prep_sides(vh, hk))) return err;
     HIPOK(hipEventRecord(c.slice_hashed[k], hk), "record");
   }
   if (K > 1)
     for (int k = 0; k < K; k++) HIPOK(hipStreamWaitEvent(s0, c.slice_hashed[k], 0), "wait hash side");
-  if ((err = launch_main(va, s0))) return err;
-  if (!zc_acc) HIPOK(hipMemcpyAsync(h_acc, d_acc, n, hipMemcpyDeviceToHost, s0), "d2h accept");
+  if ((err = launch_main(va, s0)) || (err = sink_d2h(v, s0))) return err;
   HIPOK(hipEventRecord(c.st_done, s0), "record scratch");
   HIPOK(hipStreamWaitEvent(c.stream, c.st_done, 0), "join");
   HIPOK(hipStreamSynchronize(s0), "stream sync");
+  sink_deliver(v);
   return 0;
 }
 
@@ -1102,31 +1155,23 @@ int run_shard_quad(DevCtx& c, const uint8_t* sigs, const uint8_t* pks, const uin
     HIPOK(hipStreamWaitEvent(s, c.st_done, 0), "wait scratch");
   }
   int err;
-  QuadIn d;
-  if ((err = quad_upload(c.qblob, c.qstage, sigs, pks, msgs, off, lo, hi, s, &d))) return err;
-  const bool acc_pinned = is_pinned(accept + lo);
-  if (!acc_pinned && c.acc_host.ensure(n)) return EDV_E_OOM;
-  uint8_t* h_acc = acc_pinned ? accept + lo : static_cast<uint8_t*>(c.acc_host.p);
-  void* zc = acc_pinned ? nullptr : c.acc_host.dev;
-  if (acc_pinned && (hipHostGetDevicePointer(&zc, h_acc, 0) != hipSuccess || !zc)) {
-    (void)hipGetLastError();
-    zc = nullptr;
-  }
-  if (!zc && c.acc.ensure(n)) return EDV_E_OOM;
-  uint8_t* d_acc = zc ? static_cast<uint8_t*>(zc) : static_cast<uint8_t*>(c.acc.p);
-  if ((err = launch_quad(c, c.qtab, d.sigs, d.pks, d.msgs, d.off, mbase, n, d_acc, s))) return err;
-  if (!zc) HIPOK(hipMemcpyAsync(h_acc, d_acc, n, hipMemcpyDeviceToHost, s), "d2h accept");
+  DevIn d;
+  VerdictSink v;
+  if ((err = quad_upload(c.qblob, c.qstage, host_in(sigs, pks, msgs, off, lo, hi), s, &d)) ||
+      (err = sink_open(v, accept + lo, n, c.acc_host, c.acc)) ||
+      (err = launch_quad(c, c.qtab, d.sigs, d.pks, d.msgs, d.off, mbase, n, v.dev, s)) || (err = sink_d2h(v, s)))
+    return err;
   if (scratch) HIPOK(hipEventRecord(c.st_done, s), "record scratch");
   HIPOK(hipStreamSynchronize(s), "stream sync");
-  if (!acc_pinned) memcpy(accept + lo, h_acc, n);
+  sink_deliver(v);
   return 0;
 }
 
-// One shard on one device, host buffers: sub-batches of P requests go round
-// robin over the kQ host-path streams; per sub-batch: H2D copies (straight
-// from the caller's memory when it is pinned, else through this stream's
-// pinned slot, filled by a parallel memcpy while earlier sub-batches run),
-// [length buckets,] prep, main, D2H of its accept bytes.  Caller holds c.mu.
+// One shard on one device, host buffers: one sub-batch on the field path, or
+// sub-batches of P requests alternating over two streams (sub_split); per
+// sub-batch: H2D copies (straight from the caller's memory when it is pinned,
+// else through this stream's pinned slot, filled by a parallel memcpy while
+// earlier sub-batches run), [length buckets,] prep, main, D2H of its accept bytes.  Caller holds c.mu.
 // uniform: 1 = every message of the whole batch has one SHA-512 block count
 // (known from the argument check), 0 = not, so the shard is scanned for it;
 // -1 = the offsets are not checked yet (a large one-shard call: the field path
@@ -1142,12 +1187,7 @@ int run_shard(DevCtx& c, const uint8_t* sigs, const uint8_t* pks, const uint8_t*
   // as a 16k sub-batch still takes a whole batch's latency at one wave per
   // SIMD.  A larger shard alternates two streams of half-chunk sub-batches, so
   // the H2D copy of one overlaps the kernels of the other.
-  const int Q = (n > c.chunk && c.chunk >= 2 * uint64_t(kBlock)) ? 2 : 1;
-  const uint64_t pmax = c.chunk / Q;
-  uint64_t P = (n + Q - 1) / Q;
-  P = ((P + 63) / 64) * 64;
-  if (P > pmax) P = pmax;
-  const uint64_t nsub = (n + P - 1) / P;
+  const auto [Q, pmax, P, nsub] = sub_split(n, c.chunk, kBlock);
   if (uniform < 0 && nsub != 1) {
     const OffScan sc = scan_offsets(off, lo, hi);
     if (!sc.ok) return set_err(EDV_E_ARG, "msg_off not non-decreasing");
@@ -1158,80 +1198,55 @@ int run_shard(DevCtx& c, const uint8_t* sigs, const uint8_t* pks, const uint8_t*
   if (c.sigs.ensure(n * 64) || c.pks.ensure(n * 32) || c.msgs.ensure(mbytes + 64) ||
       c.off.ensure((n + nsub) * 8) || c.acc.ensure(n))
     return EDV_E_OOM;
-  const bool pinned = is_pinned(sigs + 64 * lo) && is_pinned(pks + 32 * lo) && is_pinned(off + lo) &&
-                      (mbytes == 0 || is_pinned(msgs + mbase));
-  const bool acc_pinned = is_pinned(accept + lo);
-  if (!acc_pinned && c.acc_host.ensure(n)) return EDV_E_OOM;
-  // bucket by SHA block count only when the shard's messages differ in block count
-  const uint32_t flags = uniform == 0 ? EDV_FLAG_BUCKETS : EDV_FLAG_UNIFORM_LENGTH;
-  uint8_t* d_sigs = static_cast<uint8_t*>(c.sigs.p);
-  uint8_t* d_pks = static_cast<uint8_t*>(c.pks.p);
-  uint8_t* d_msgs = static_cast<uint8_t*>(c.msgs.p);
-  uint64_t* d_off = static_cast<uint64_t*>(c.off.p);
-  uint8_t* d_acc = static_cast<uint8_t*>(c.acc.p);
-  uint8_t* h_acc = acc_pinned ? accept + lo : static_cast<uint8_t*>(c.acc_host.p);
-  int err;
+  const bool pinned = inputs_pinned(host_in(sigs, pks, msgs, off, lo, hi));
   // One chunk: copied field by field, the point sides starting before the
   // messages are in.
-  if (nsub == 1) {
-    if ((err = run_shard_fields(c, sigs, pks, msgs, off, lo, hi, pinned, uniform, d_sigs, d_pks, d_msgs, d_off,
-                                d_acc, h_acc)))
-      return err;
-    if (!acc_pinned) memcpy(accept + lo, h_acc, n);
-    return 0;
-  }
-  hipStream_t* hs = c.hs;
+  if (nsub == 1)
+    return run_shard_fields(c, host_in(sigs, pks, msgs, off, lo, hi), off, lo, hi, pinned, uniform, accept + lo);
+  // bucket by SHA block count only when the shard's messages differ in block count
+  const uint32_t flags = uniform == 0 ? EDV_FLAG_BUCKETS : EDV_FLAG_UNIFORM_LENGTH;
+  uint8_t *d_sigs = static_cast<uint8_t*>(c.sigs.p), *d_pks = static_cast<uint8_t*>(c.pks.p),
+          *d_msgs = static_cast<uint8_t*>(c.msgs.p);
+  uint64_t* d_off = static_cast<uint64_t*>(c.off.p);
+  int err;
+  VerdictSink v;  // never zero-copy here: each sub-batch's verdicts are copied back from c.acc as it finishes
+  if ((err = sink_host(v, accept + lo, n, c.acc_host))) return err;
+  v.dev = static_cast<uint8_t*>(c.acc.p);
   if ((err = grow_state(c, uint64_t(Q) * pmax))) return err;  // sub-batch stream q uses slots [q pmax, (q + 1) pmax)
-  for (int q = 0; q < Q; q++) HIPOK(hipStreamWaitEvent(hs[q], c.st_done, 0), "wait scratch");
+  for (int q = 0; q < Q; q++) HIPOK(hipStreamWaitEvent(c.hs[q], c.st_done, 0), "wait scratch");
   for (uint64_t k = 0; k < nsub; k++) {
     const int q = int(k % Q);
-    hipStream_t s = hs[q];
+    hipStream_t s = c.hs[q];
     const uint64_t a = lo + k * P, b = (a + P) < hi ? (a + P) : hi, cnt = b - a;
-    const uint64_t mA = off[a], mB = off[b];
     // sub-batch k's offsets live at d_off + (a - lo) + k: one private n+1 window each
     uint64_t* d_o = d_off + (a - lo) + k;
-    const uint8_t *src_s = sigs + 64 * a, *src_p = pks + 32 * a, *src_m = msgs + mA;
-    const uint64_t* src_o = off + a;
+    HostIn h = host_in(sigs, pks, msgs, off, a, b);
     if (!pinned) {
       // pageable: staged through this stream's pinned slot (a parallel memcpy),
       // then copied by DMA.  (Staging in four parts with each part's H2D queued
       // as soon as it was staged measured slower at C2, 2.43 vs 1.78 ms per 64k:
       // profiles/r02/e2e_probe_s6.json.)
-      PinnedBuf& sl = c.stage[q];
       HIPOK(hipEventSynchronize(c.hs_staged[q]), "stage wait");  // the slot's previous H2D is done
-      if (sl.ensure(cnt * 96 + (cnt + 1) * 8 + (mB - mA))) return EDV_E_OOM;
-      uint8_t* p = static_cast<uint8_t*>(sl.p);
-      uint8_t *ps = p, *pp = p + cnt * 64, *po = p + cnt * 96, *pm = p + cnt * 96 + (cnt + 1) * 8;
-      par_copy({{ps, src_s, 64 * cnt}, {pp, src_p, 32 * cnt}, {po, reinterpret_cast<const uint8_t*>(src_o), 8 * (cnt + 1)},
-                {pm, src_m, mB - mA}});
-      HIPOK(hipMemcpyAsync(d_sigs + 64 * (a - lo), ps, 64 * cnt, hipMemcpyHostToDevice, s), "h2d sigs");
-      HIPOK(hipMemcpyAsync(d_pks + 32 * (a - lo), pp, 32 * cnt, hipMemcpyHostToDevice, s), "h2d pks");
-      HIPOK(hipMemcpyAsync(d_o, po, 8 * (cnt + 1), hipMemcpyHostToDevice, s), "h2d off");
-      if (mB > mA) HIPOK(hipMemcpyAsync(d_msgs + (mA - mbase), pm, mB - mA, hipMemcpyHostToDevice, s), "h2d msgs");
-    } else {
-      HIPOK(hipMemcpyAsync(d_sigs + 64 * (a - lo), src_s, cnt * 64, hipMemcpyHostToDevice, s), "h2d sigs");
-      HIPOK(hipMemcpyAsync(d_pks + 32 * (a - lo), src_p, cnt * 32, hipMemcpyHostToDevice, s), "h2d pks");
-      HIPOK(hipMemcpyAsync(d_o, src_o, (cnt + 1) * 8, hipMemcpyHostToDevice, s), "h2d off");
-      if (mB > mA)
-        HIPOK(hipMemcpyAsync(d_msgs + (mA - mbase), src_m, mB - mA, hipMemcpyHostToDevice, s), "h2d msgs");
+      if ((err = stage_inputs(c.stage[q], h, true))) return err;
     }
+    if ((err = upload(h, false, 0, d_sigs + 64 * (a - lo), d_pks + 32 * (a - lo), d_o, d_msgs + (h.mbase - mbase), s)))
+      return err;
     if (!pinned) HIPOK(hipEventRecord(c.hs_staged[q], s), "record");
     const bool bucket = bucketing_enabled(c, flags);
-    VerifyArgs va = make_args(c, c.st, d_sigs + 64 * (a - lo), d_pks + 32 * (a - lo), d_msgs, d_o, mbase,
-                              d_acc + (a - lo), bucket, uint64_t(q) * pmax, n);
+    const VerifyArgs va = make_args(c, c.st, d_sigs + 64 * (a - lo), d_pks + 32 * (a - lo), d_msgs, d_o, mbase,
+                                    v.dev + (a - lo), bucket, uint64_t(q) * pmax, n);
     if (!va.btab) return no_tables(c);
-    va.n = cnt;
-    if ((err = launch_prep(bucket_ctr(c.st, q), va, d_o, bucket, s)) || (err = launch_main(va, s))) return err;
-    HIPOK(hipMemcpyAsync(h_acc + (a - lo), d_acc + (a - lo), cnt, hipMemcpyDeviceToHost, s), "d2h accept");
+    if ((err = walk_chunks(bucket_ctr(c.st, q), va, bucket, cnt, cnt, s))) return err;
+    HIPOK(hipMemcpyAsync(v.host + (a - lo), v.dev + (a - lo), cnt, hipMemcpyDeviceToHost, s), "d2h accept");
   }
   // join the sub-batch streams into the library stream: the scratch's next user waits for all of them
   for (int q = 0; q < Q; q++) {
-    HIPOK(hipEventRecord(c.hs_end[q], hs[q]), "record");
+    HIPOK(hipEventRecord(c.hs_end[q], c.hs[q]), "record");
     HIPOK(hipStreamWaitEvent(c.stream, c.hs_end[q], 0), "wait");
   }
   HIPOK(hipEventRecord(c.st_done, c.stream), "record scratch");
   HIPOK(hipStreamSynchronize(c.stream), "stream sync");
-  if (!acc_pinned) memcpy(accept + lo, h_acc, n);
+  sink_deliver(v);
   return 0;
 }
 
@@ -1356,53 +1371,40 @@ int async_complete(DevCtx& c, DevCtx::AsyncSlot& s) {
     return set_err(EDV_E_HIP, "async batch failed (injected by edv_test_fail_async)");
   }
 #endif
-  if (!s.acc_pinned) memcpy(s.accept, s.acc_host.p, s.n);
+  sink_deliver(s.verdicts);
   if (s.digests && !s.dig_pinned) memcpy(s.digests, s.dig_host.p, 32 * s.n);
   s.ticket = -1;
   return 0;
 }
 
-// An asynchronous latency-path batch on slot s (ticket t, the slot's previous
-// batch complete): packed into the slot's pinned staging, one DMA and the quad
-// kernel on the slot's own stream, verdicts (and digests) as submit_async's.
-int submit_async_quad(DevCtx& c, DevCtx::AsyncSlot& s, int64_t t, const uint8_t* sigs, const uint8_t* pks,
-                      const uint8_t* msgs, const uint64_t* off, uint64_t n, uint8_t* accept, uint8_t* digests,
-                      int64_t* ticket) {
-  const uint64_t mbase = off[0];
-  if (!s.st) HIPOK(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking), "hipStreamCreate");
-  if (s.acc.ensure(n) || (digests && s.dig.ensure(32 * n))) return EDV_E_OOM;
-  s.dig_pinned = digests && is_pinned(digests);
-  if (digests && !s.dig_pinned && s.dig_host.ensure(32 * n)) return EDV_E_OOM;
-  s.acc_pinned = is_pinned(accept);
-  if (!s.acc_pinned && s.acc_host.ensure(n)) return EDV_E_OOM;
+// What both submission routes end with, on stream ks, for batch t on slot s
+// with its inputs d on the device: the verify kernels (launch(d_acc): the
+// route's), the D2H of the verdicts, the digests if asked for, the slot's done
+// event, its bookkeeping and the ticket.
+template <class Launch>
+int async_run(DevCtx& c, DevCtx::AsyncSlot& s, int64_t t, const DevIn& d, uint64_t mbase, uint64_t n, uint8_t* accept,
+              uint8_t* digests, hipStream_t ks, int64_t* ticket, Launch launch) {
   int err;
-  QuadIn d;
-  if ((err = quad_upload(s.msgs, s.stage, sigs, pks, msgs, off, 0, n, s.st, &d))) return err;
-  uint8_t* h_acc = s.acc_pinned ? accept : static_cast<uint8_t*>(s.acc_host.p);
-  void* zc = nullptr;
-  if (hipHostGetDevicePointer(&zc, h_acc, 0) != hipSuccess || !zc) {
-    (void)hipGetLastError();
-    zc = nullptr;
-  }
-  uint8_t* d_acc = zc ? static_cast<uint8_t*>(zc) : static_cast<uint8_t*>(s.acc.p);
+  // verdicts written by the kernels straight into page-locked host memory, as
+  // in the synchronous path: no D2H between this batch's main kernel and the
+  // next batch's prep on the stream (a C2 stream of batches 0.945 -> 0.965x
+  // device-resident, profiles/r05/ab_async_s7.jsonl)
+  if ((err = sink_open(s.verdicts, accept, n, s.acc_host, s.acc))) return err;
   bool skip = false;  // edv_test_fail_async (measurement build): no kernels, and the wait fails
 #ifdef EDV_MEASUREMENT_API
   skip = s.injected = (t == c.inject_fail);
 #endif
-  if (!skip && (err = launch_quad(c, s.qtab, d.sigs, d.pks, d.msgs, d.off, mbase, n, d_acc, s.st))) return err;
-  if (!zc) HIPOK(hipMemcpyAsync(h_acc, d_acc, n, hipMemcpyDeviceToHost, s.st), "d2h accept");
+  if ((!skip && (err = launch(s.verdicts.dev))) || (err = sink_d2h(s.verdicts, ks))) return err;
   if (digests && !skip) {
     // Request.getDigest of requests whose signing bytes ARE the message (the
     // caller decides which): SHA-256 of the message bytes already on the device
     uint8_t* d_dig = static_cast<uint8_t*>(s.dig.p);
-    if ((err = launch_sha256(d.msgs, d.off, mbase, n, d_dig, s.st)))
-      return err;
+    if ((err = launch_sha256(d.msgs, d.off, mbase, n, d_dig, ks))) return err;
     uint8_t* h_dig = s.dig_pinned ? digests : static_cast<uint8_t*>(s.dig_host.p);
-    HIPOK(hipMemcpyAsync(h_dig, d_dig, 32 * n, hipMemcpyDeviceToHost, s.st), "d2h digests");
+    HIPOK(hipMemcpyAsync(h_dig, d_dig, 32 * n, hipMemcpyDeviceToHost, ks), "d2h digests");
   }
-  HIPOK(hipEventRecord(s.done, s.st), "record");
+  HIPOK(hipEventRecord(s.done, ks), "record");
   s.ticket = t;
-  s.accept = accept;
   s.digests = digests;
   s.n = n;
   *ticket = c.ledger.issue();
@@ -1428,75 +1430,36 @@ int submit_async(DevCtx& c, const uint8_t* sigs, const uint8_t* pks, const uint8
   if (s.sigs.ensure(n * 64) || s.pks.ensure(n * 32) || s.msgs.ensure(mbytes + 64) || s.off.ensure((n + 1) * 8) ||
       s.acc.ensure(n) || (digests && s.dig.ensure(32 * n)))
     return EDV_E_OOM;
-  // the latency path: the slot's pinned staging packed, one DMA, the quad kernel
-  if (n <= c.quad_max) return submit_async_quad(c, s, t, sigs, pks, msgs, off, n, accept, digests, ticket);
-  // small batch: everything on the slot's stream and scratch (see kSmallAsync)
-  const bool own = n <= kSmallAsync;
-  if (own) {
-    if (!s.st) HIPOK(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking), "hipStreamCreate");
-    if (s.cb.ensure(n, kSmallAsync)) return EDV_E_OOM;  // the slot's previous batch is complete
-  }
-  const hipStream_t cs = own ? s.st : c.hcp, ks = own ? s.st : c.hac;
   s.dig_pinned = digests && is_pinned(digests);
   if (digests && !s.dig_pinned && s.dig_host.ensure(32 * n)) return EDV_E_OOM;
-  const bool pinned = is_pinned(sigs) && is_pinned(pks) && is_pinned(off) && (mbytes == 0 || is_pinned(msgs + mbase));
-  s.acc_pinned = is_pinned(accept);
-  if (!s.acc_pinned && s.acc_host.ensure(n)) return EDV_E_OOM;
-  const bool varied = !uniform;
-  const uint32_t lflags = varied ? EDV_FLAG_BUCKETS : EDV_FLAG_UNIFORM_LENGTH;
-  const uint8_t *src_s = sigs, *src_p = pks, *src_m = msgs + mbase;
-  const uint8_t* src_o = reinterpret_cast<const uint8_t*>(off);
-  if (!pinned) {
-    if (s.stage.ensure(n * 96 + (n + 1) * 8 + mbytes)) return EDV_E_OOM;
-    uint8_t* p = static_cast<uint8_t*>(s.stage.p);
-    par_copy({{p, sigs, 64 * n}, {p + 64 * n, pks, 32 * n}, {p + 96 * n, src_o, 8 * (n + 1)},
-              {p + 96 * n + 8 * (n + 1), src_m, mbytes}});
-    src_s = p; src_p = p + 64 * n; src_o = p + 96 * n; src_m = p + 96 * n + 8 * (n + 1);
+  HostIn h = host_in(sigs, pks, msgs, off, 0, n);
+  // small batch: everything on the slot's stream and scratch (see kSmallAsync)
+  const bool own = n <= kSmallAsync, quad = n <= c.quad_max;
+  if ((own || quad) && !s.st) HIPOK(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking), "hipStreamCreate");
+  // the latency path: inputs packed into the slot's pinned staging and read
+  // there, or DMA'd (quad_upload), the quad kernel on the slot's own stream
+  if (quad) {
+    DevIn d;
+    if ((err = quad_upload(s.msgs, s.stage, h, s.st, &d))) return err;
+    return async_run(c, s, t, d, mbase, n, accept, digests, s.st, ticket, [&](uint8_t* d_acc) {
+      return launch_quad(c, s.qtab, d.sigs, d.pks, d.msgs, d.off, mbase, n, d_acc, s.st);
+    });
   }
-  uint8_t* d_sigs = static_cast<uint8_t*>(s.sigs.p);
-  uint8_t* d_pks = static_cast<uint8_t*>(s.pks.p);
-  uint8_t* d_msgs = static_cast<uint8_t*>(s.msgs.p);
-  uint64_t* d_off = static_cast<uint64_t*>(s.off.p);
-  uint8_t* d_acc = static_cast<uint8_t*>(s.acc.p);
-  HIPOK(hipMemcpyAsync(d_sigs, src_s, n * 64, hipMemcpyHostToDevice, cs), "h2d sigs");
-  HIPOK(hipMemcpyAsync(d_pks, src_p, n * 32, hipMemcpyHostToDevice, cs), "h2d pks");
-  HIPOK(hipMemcpyAsync(d_off, src_o, (n + 1) * 8, hipMemcpyHostToDevice, cs), "h2d off");
-  if (mbytes) HIPOK(hipMemcpyAsync(d_msgs, src_m, mbytes, hipMemcpyHostToDevice, cs), "h2d msgs");
+  if (own && s.cb.ensure(n, kSmallAsync)) return EDV_E_OOM;  // the slot's previous batch is complete
+  const hipStream_t cs = own ? s.st : c.hcp, ks = own ? s.st : c.hac;
+  const uint32_t lflags = uniform ? EDV_FLAG_UNIFORM_LENGTH : EDV_FLAG_BUCKETS;
+  if (!inputs_pinned(h) && (err = stage_inputs(s.stage, h, true))) return err;
+  const DevIn d = {static_cast<uint8_t*>(s.sigs.p), static_cast<uint8_t*>(s.pks.p), static_cast<uint8_t*>(s.msgs.p),
+                   static_cast<uint64_t*>(s.off.p)};
+  if ((err = upload(h, false, 0, s.sigs.p, s.pks.p, s.off.p, s.msgs.p, cs))) return err;
   if (!own) {
     HIPOK(hipEventRecord(s.copied, c.hcp), "record");
     HIPOK(hipStreamWaitEvent(c.hac, s.copied, 0), "wait copy");
   }
-  uint8_t* h_acc = s.acc_pinned ? accept : static_cast<uint8_t*>(s.acc_host.p);
-  // verdicts written by the kernels straight into page-locked host memory, as
-  // in the synchronous path: no D2H between this batch's main kernel and the
-  // next batch's prep on the stream (a C2 stream of batches 0.945 -> 0.965x
-  // device-resident, profiles/r05/ab_async_s7.jsonl)
-  void* zc = nullptr;
-  if (hipHostGetDevicePointer(&zc, h_acc, 0) == hipSuccess && zc) d_acc = static_cast<uint8_t*>(zc);
-  else (void)hipGetLastError();
-  bool skip = false;  // edv_test_fail_async (measurement build): no kernels, and the wait fails
-#ifdef EDV_MEASUREMENT_API
-  skip = s.injected = (t == c.inject_fail);
-#endif
-  if (!skip && (err = own ? launch_own(c, s.cb, d_sigs, d_pks, d_msgs, d_off, mbase, n, d_acc, ks, lflags)
-                          : launch(c, d_sigs, d_pks, d_msgs, d_off, mbase, n, d_acc, ks, lflags)))
-    return err;
-  if (!zc) HIPOK(hipMemcpyAsync(h_acc, d_acc, n, hipMemcpyDeviceToHost, ks), "d2h accept");
-  if (digests && !skip) {
-    // Request.getDigest of requests whose signing bytes ARE the message (the
-    // caller decides which): SHA-256 of the same resident message bytes
-    uint8_t* d_dig = static_cast<uint8_t*>(s.dig.p);
-    if ((err = launch_sha256(d_msgs, d_off, mbase, n, d_dig, ks))) return err;
-    uint8_t* h_dig = s.dig_pinned ? digests : static_cast<uint8_t*>(s.dig_host.p);
-    HIPOK(hipMemcpyAsync(h_dig, d_dig, 32 * n, hipMemcpyDeviceToHost, ks), "d2h digests");
-  }
-  HIPOK(hipEventRecord(s.done, ks), "record");
-  s.ticket = t;
-  s.accept = accept;
-  s.digests = digests;
-  s.n = n;
-  *ticket = c.ledger.issue();
-  return 0;
+  return async_run(c, s, t, d, mbase, n, accept, digests, ks, ticket, [&](uint8_t* d_acc) {
+    return own ? launch_own(c, s.cb, d.sigs, d.pks, d.msgs, d.off, mbase, n, d_acc, ks, lflags)
+               : launch(c, d.sigs, d.pks, d.msgs, d.off, mbase, n, d_acc, ks, lflags);
+  });
 }
 
 // Per-verify cost in SHA-512-block units for the shard split: W(m) of SURVEY.md
@@ -1694,7 +1657,6 @@ int check_dev_align(const void* d_sigs, const void* d_pks, const void* d_off) {
   return 0;
 }
 
-
 // ---- context lifecycle (edv_prepare, edv_self_test, edv_trim, edv_release)
 // An asynchronous batch not yet handed over, or a pipelined batch not yet
 // synced, still owns caller buffers: the context cannot be trimmed or released.
@@ -1704,69 +1666,58 @@ bool ctx_busy(const DevCtx& c) {
   return c.pending[0] || c.pending[1];
 }
 
-// Message bytes per request the warm-up batches of edv_prepare carry, and the
-// most a buffer may hold per request of keep_batch and still survive edv_trim.
+// Message bytes per request the warm-up batches of edv_prepare carry (what a
+// buffer may hold per request of keep_batch and still survive edv_trim:
+// kTrimMsgBytes, edv_hostplan.h).
 constexpr uint64_t kPrepareMsgBytes = 512;
-constexpr uint64_t kTrimMsgBytes = 4096;
 constexpr uint64_t kPrepareMax = uint64_t(1) << 20;  // a warm-up batch is built in host memory: 0.7 GB here
 
 // Free what is larger than a batch of `keep` requests needs (0: everything),
 // after the context is drained.  Caller holds c.mu; the current device is c.phys.
 void trim_buffers(DevCtx& c, uint64_t keep) {
   const uint64_t k = keep;
-  uint64_t slots = 0;  // the ChunkBufs capacity such a batch grows a set to (ChunkBufs::ensure)
-  if (k) {
-    slots = 4096;
-    while (slots < k && slots < c.chunk) slots <<= 1;
-    if (slots > c.chunk) slots = c.chunk;
-  }
-  const uint64_t packed = k ? 104 * k + 8 + 4096 : 0;               // signatures | keys | offsets in one span
-  const uint64_t blob = k ? packed + k * kTrimMsgBytes + 64 : 0;     // ... and the messages
-  const uint64_t pinned = blob + blob / 4 + (k ? 4096 : 0);          // PinnedBuf's headroom
+  const TrimLimits t = trim_limits(keep, c.chunk);  // edv_hostplan.h
   const uint64_t kq = k < kQuadMaxLimit ? k : kQuadMaxLimit;
   const uint64_t qtab = kq > kRtlMax ? (kq + 63) / 64 * 64 * kQSigWords * 4 : 0;
-  auto dev = [](DevBuf& b, uint64_t limit) {
-    if (b.cap > limit) b.release();
-  };
-  auto pin = [](PinnedBuf& b, uint64_t limit) {
+  auto dev = [](auto& b, uint64_t limit) {  // a DevBuf or a PinnedBuf: freed if larger
     if (b.cap > limit) b.release();
   };
   auto set = [&](ChunkBufs& b) {
-    if (b.cap > slots) b.release();
+    if (b.cap > t.slots) b.release();
   };
   set(c.st);
   set(c.pst[0]);
   set(c.pst[1]);
-  dev(c.sigs, 64 * k);
-  dev(c.pks, 32 * k);
-  dev(c.msgs, k * kTrimMsgBytes + 64);
-  dev(c.off, k ? 8 * (k + k / (c.chunk / 2 ? c.chunk / 2 : 1) + 2) : 0);
-  dev(c.acc, k);
-  dev(c.fblob, packed);
-  dev(c.qblob, blob);
+  dev(c.sigs, t.sigs);
+  dev(c.pks, t.pks);
+  dev(c.msgs, t.msgs);
+  dev(c.off, t.off);
+  dev(c.acc, t.acc);
+  dev(c.fblob, t.packed);
+  dev(c.qblob, t.blob);
   dev(c.qtab, qtab);
-  pin(c.qstage, pinned);
-  pin(c.acc_host, k + k / 4 + (k ? 4096 : 0));
-  for (int q = 0; q < kQ; q++) pin(c.stage[q], pinned);
+  dev(c.qstage, t.stage);
+  dev(c.acc_host, t.acc_host);
+  for (int q = 0; q < kQ; q++) dev(c.stage[q], t.stage);
   // the Merkle buffers: what extending any tree by k leaves of kTrimMsgBytes can need
   dev(c.mk_roots, k ? 32 * (k / (kMerkleT - 1) + 16) : 0);
-  dev(c.mk_leaves, k ? k * kTrimMsgBytes + 64 : 0);
-  dev(c.mk_off, k ? 8 * (k + 1) : 0);
+  dev(c.mk_leaves, k ? t.msgs : 0);
+  dev(c.mk_off, t.slot_off);
   dev(c.mk_hashes, k ? 32 * (2 * kMerkleMaxHashes + 2) : 0);
   dev(c.mk_leafh, 32 * k);
   dev(c.mk_nodeh, 32 * k);
   for (auto& a : c.as) {
     set(a.cb);
-    dev(a.sigs, 64 * k);
-    dev(a.pks, 32 * k);
-    dev(a.msgs, blob);  // the latency path packs the whole batch here
-    dev(a.off, k ? 8 * (k + 1) : 0);
-    dev(a.acc, k);
-    dev(a.dig, 32 * k);
+    dev(a.sigs, t.sigs);
+    dev(a.pks, t.pks);
+    dev(a.msgs, t.blob);  // the latency path packs the whole batch here
+    dev(a.off, t.slot_off);
+    dev(a.acc, t.acc);
+    dev(a.dig, t.dig);
     dev(a.qtab, qtab);
-    pin(a.stage, pinned);
-    pin(a.acc_host, k + k / 4 + (k ? 4096 : 0));
-    pin(a.dig_host, 32 * k + 8 * k + (k ? 4096 : 0));
+    dev(a.stage, t.stage);
+    dev(a.acc_host, t.acc_host);
+    dev(a.dig_host, t.dig_host);
   }
 }
 
@@ -1794,47 +1745,21 @@ void ctx_destroy(DevCtx& c) {
   trim_tables(c, 0, true);
   if (c.comb) (void)hipFree(c.comb);
   c.comb = nullptr;
-  auto ev = [](hipEvent_t& e) {
+  for_each_event(c, [](hipEvent_t& e, bool) {
     if (e) (void)hipEventDestroy(e);
     e = nullptr;
-  };
-  auto st = [](hipStream_t& x) {
-    if (x) (void)hipStreamDestroy(x);
-    x = nullptr;
-  };
-  for (int q = 0; q < kQ; q++) {
-    st(c.hs[q]);
-    ev(c.hs_staged[q]);
-    ev(c.hs_end[q]);
-    ev(c.part_copied[q]);
-    ev(c.part_prepped[q]);
-  }
-  for (int k = 0; k < kSlices; k++) {
-    ev(c.slice_copied[k]);
-    ev(c.slice_hashed[k]);
-  }
+  });
+  for_each_stream(c, [](hipStream_t& s, bool) {
+    if (s) (void)hipStreamDestroy(s);
+    s = nullptr;
+  });
   for (auto& a : c.as) {
-    st(a.st);
-    ev(a.copied);
-    ev(a.done);
     a.ticket = -1;
-    a.accept = a.digests = nullptr;
+    a.verdicts = VerdictSink();
+    a.digests = nullptr;
     a.n = 0;
   }
-  for (int b = 0; b < 2; b++) {
-    ev(c.prep_done[b]);
-    ev(c.main_done[b]);
-    ev(c.perm_done[b]);
-    c.pending[b] = false;
-  }
-  ev(c.inputs_ready);
-  ev(c.st_done);
-  ev(c.mk_done);
-  st(c.sp);
-  st(c.sm);
-  st(c.hcp);
-  st(c.hac);
-  st(c.stream);
+  c.pending[0] = c.pending[1] = false;
   c.pipe_ready = false;
   c.next = 0;
   c.ready = false;
@@ -1949,9 +1874,6 @@ int warm_up(DevCtx& c, uint64_t n, bool async, bool pin) {
     DevCtx::AsyncSlot& s = c.as[c.ledger.next % kAsyncSlots];
     if ((err = submit_async(c, b.sigs, b.pks, b.msgs, b.off, n, b.accept, b.digests, true, &t))) {
       quiesce(c);
-      for (auto& a : c.as)
-        if (a.st) (void)hipStreamSynchronize(a.st);
-      (void)hipGetLastError();
       return err;
     }
     if ((err = async_complete(c, s))) return err;
@@ -1959,6 +1881,36 @@ int warm_up(DevCtx& c, uint64_t n, bool async, bool pin) {
   return 0;
 }
 
+// edv_trim / edv_release: f on the context of `device`, idle and drained, under its lock (no context: nothing to do)
+template <class F>
+int on_drained_ctx(int device, const char* busy, F f) {
+  g_err.clear();
+  int err = 0;
+  DevCtx* c = get_ctx(device, &err);
+  if (!c) return err;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (c->ready) {
+    if (ctx_busy(*c)) return set_err(EDV_E_BUSY, busy);
+    HIPOK(hipSetDevice(c->phys), "hipSetDevice");
+    if ((err = drain(*c))) return err;
+    f(*c);
+  }
+  c->sb_failed = false;
+  return 0;
+}
+
+// The edv_set_* of a setting that needs no context made: set under the device's lock, if the value is valid
+template <class F>
+int set_on_ctx(int device, bool valid, const char* what, F set) {
+  g_err.clear();
+  int err = 0;
+  DevCtx* c = get_ctx(device, &err);
+  if (!c) return err;
+  if (!valid) return set_err(EDV_E_ARG, what);
+  std::lock_guard<std::mutex> lk(c->mu);
+  set(*c);
+  return 0;
+}
 }  // namespace
 
 // ------------------------------------------------------------------ C-ABI
@@ -2074,11 +2026,7 @@ int edv_verify_digest_batch_async(const uint8_t* sigs, const uint8_t* pks, const
   if ((err = submit_async(*cl.c, sigs, pks, msgs, msg_off, n, accept, digests, uniform, ticket))) {
     // whatever was queued before the failure may still read the caller's
     // buffers: let it finish before the caller gets the error back
-    (void)hipStreamSynchronize(cl.c->hcp);
-    (void)hipStreamSynchronize(cl.c->hac);
-    for (auto& s : cl.c->as)
-      if (s.st) (void)hipStreamSynchronize(s.st);
-    (void)hipGetLastError();
+    quiesce(*cl.c);
   }
   return err;
 }
@@ -2270,7 +2218,6 @@ int edv_pipeline_sync(int device) {
   return 0;
 }
 
-
 static int ensure_comb(DevCtx& c) {
   if (c.comb) return 0;
   int32_t* p = nullptr;
@@ -2336,38 +2283,17 @@ int edv_set_chunk(int device, uint64_t chunk) {
 }
 
 int edv_set_host_slices(int device, int slices) {
-  g_err.clear();
-  int err = 0;
-  DevCtx* c = get_ctx(device, &err);
-  if (!c) return err;
-  if (slices < 0 || slices > kSlices) return set_err(EDV_E_ARG, "slices must be 0..8");
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->host_slices = slices;
-  return 0;
+  return set_on_ctx(device, slices >= 0 && slices <= kSlices, "slices must be 0..8",
+                    [&](DevCtx& c) { c.host_slices = slices; });
 }
-
 int edv_set_latency_path(int device, uint64_t max_requests) {
-  g_err.clear();
-  int err = 0;
-  DevCtx* c = get_ctx(device, &err);
-  if (!c) return err;
-  if (max_requests > kQuadMaxLimit) return set_err(EDV_E_ARG, "latency path is for batches of at most 16,384");
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->quad_max = max_requests;
-  return 0;
+  return set_on_ctx(device, max_requests <= kQuadMaxLimit, "latency path is for batches of at most 16,384",
+                    [&](DevCtx& c) { c.quad_max = max_requests; });
 }
-
 int edv_set_length_buckets(int device, int mode) {
-  g_err.clear();
-  int err = 0;
-  DevCtx* c = get_ctx(device, &err);
-  if (!c) return err;
-  if (mode < 0 || mode > 2) return set_err(EDV_E_ARG, "length-bucket mode must be 0, 1 or 2");
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->length_buckets = mode;
-  return 0;
+  return set_on_ctx(device, mode >= 0 && mode <= 2, "length-bucket mode must be 0, 1 or 2",
+                    [&](DevCtx& c) { c.length_buckets = mode; });
 }
-
 
 int edv_set_table_policy(int device, int policy) {
   g_err.clear();
@@ -2434,40 +2360,13 @@ int edv_prepare(int device, uint64_t max_batch, uint32_t flags) {
 }
 
 int edv_trim(int device, uint64_t keep_batch) {
-  g_err.clear();
-  int err = 0;
-  DevCtx* c = get_ctx(device, &err);
-  if (!c) return err;
-  std::lock_guard<std::mutex> lk(c->mu);
-  if (!c->ready) {
-    c->sb_failed = false;
-    return 0;
-  }
-  if (ctx_busy(*c)) return set_err(EDV_E_BUSY, "trim: asynchronous or pipelined batches not yet handed over");
-  HIPOK(hipSetDevice(c->phys), "hipSetDevice");
-  if ((err = drain(*c))) return err;
-  c->sb_failed = false;
-  trim_buffers(*c, keep_batch);
-  trim_tables(*c, keep_batch, false);
-  return 0;
+  return on_drained_ctx(device, "trim: asynchronous or pipelined batches not yet handed over", [&](DevCtx& c) {
+    trim_buffers(c, keep_batch);
+    trim_tables(c, keep_batch, false);
+  });
 }
-
 int edv_release(int device) {
-  g_err.clear();
-  int err = 0;
-  DevCtx* c = get_ctx(device, &err);
-  if (!c) return err;
-  std::lock_guard<std::mutex> lk(c->mu);
-  if (!c->ready) {
-    c->sb_failed = false;
-    return 0;
-  }
-  if (ctx_busy(*c)) return set_err(EDV_E_BUSY, "release: asynchronous or pipelined batches not yet handed over");
-  HIPOK(hipSetDevice(c->phys), "hipSetDevice");
-  if ((err = drain(*c))) return err;
-  c->sb_failed = false;
-  ctx_destroy(*c);
-  return 0;
+  return on_drained_ctx(device, "release: asynchronous or pipelined batches not yet handed over", ctx_destroy);
 }
 
 int edv_dev_alloc(int device, uint64_t bytes, void** out) {

@@ -17,7 +17,7 @@ def load():
         _lib = _bind(ctypes.CDLL(os.environ["EDV_HOSTCHECK_OVERRIDE"]))  # an instrumented build (tools/asan_host.sh)
     if _lib is None:
         srcs = [os.path.join(CSRC, f) for f in ("edv_hostcheck.cpp", "edv_math.h", "edv_verify_core.h", "edv_sha256.h", "edv_ledger.h",
-                                                 "edv_probe_ops.h")]
+                                                 "edv_hostplan.h", "edv_probe_ops.h")]
         if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(s) for s in srcs):
             subprocess.check_call(["make", "-s", "-C", CSRC, "../libedv_hostcheck.so"])
         _lib = _bind(ctypes.CDLL(SO))

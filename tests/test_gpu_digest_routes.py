@@ -5,14 +5,14 @@ buffer kind, called through edv.lib() directly:
 
   route                          reached by                   n
   latency, right-to-left kernel  the default latency limit    1, 16, 17, 400
-  latency, two-walk kernel       the default latency limit    4,097
+  latency, two-walk kernel       the default latency limit    4,097, 8,193
   the slot's own stream          set_latency_path(0, 0)       1, 257, 8,192
   the shared copy/kernel streams set_latency_path(0, 0)       8,193
 
 Each (route, n) runs inputs pageable with digests pageable and with digests
 page-locked, inputs page-locked in three regions, and inputs page-locked in
 ONE region laid out sigs | pks | offsets with gaps of 16 and 8 bytes
-(quad_upload's single-copy branch), each with off[0] = 0 and off[0] = 5 (the
+(the input stager's single-copy branch, one_span of csrc/edv_hostplan.h), each with off[0] = 0 and off[0] = 5 (the
 message pointer unchanged); the latency route once more in a child process
 with EDV_QUAD_ZERO_COPY=0 (read once per process).  Every digest byte equals
 hashlib.sha256's, every verdict the checker's (libsodium where present, else
@@ -23,11 +23,14 @@ page-locked and pageable, every third without digests, handed over by slot
 reuse, by edv_wait_async out of order and by edv_query_async; and empty
 batches.
 
-Digest comparisons per run (8 buffer/offset combinations per size): latency
-route 36,248 (+ 9,062 in the child), own stream 67,600, shared streams 65,544,
+The latency route's 8,193 is past kSmallAsync: a latency-path batch runs on its
+slot's own stream at every size up to the limit.  Digest comparisons per run (8
+buffer/offset combinations per size): latency route 101,792 (+ 25,448 in the
+child), own stream 67,600, shared streams 65,544,
 slot reuse 2 x 1,801 (and 2 x 2,168 verdicts), empty 2 x 44.  Measured on
-MI355X: 14 tests in 2.0 s; the child process 0.9 s, the
-first case 0.4 s (it signs the pool's 4,097 requests), [own-8192] 0.14 s (it
+MI355X: 14 tests in 2.0 s before [latency-8193] (0.16 s)
+was added; the child process 0.9 s (1.2 s with that size), the
+first case 0.4 s (it signs the pool's 4,097 requests), [latency-8193] 0.16 s (it
 builds the corpus), every other case at most 0.04 s.
 """
 import ctypes
@@ -53,7 +56,7 @@ SPECIAL_LENS = [0, 1, 3, 54, 55, 56, 57, 63, 64, 65, 119, 120, 121, 127, 128, 12
 POOL_N = 4097
 SENT = 0xA5
 SMALL_ORDER_A = bytes.fromhex("26e8958fc2b227b045c3f489f2ef98f0d5dfac05d3c63339b13802886d53fc05")  # order 8
-LATENCY = [("latency", n) for n in (1, 16, 17, 400, 4097)]
+LATENCY = [("latency", n) for n in (1, 16, 17, 400, 4097, 8193)]
 ROUTES = LATENCY + [("own", n) for n in (1, 257, 8192)] + [("shared", 8193)]
 
 
@@ -76,14 +79,14 @@ class Batch:
                 self.want[lo:lo + n], self.digests[32 * lo:32 * (lo + n)])
 
 
-def signed_pool(n=POOL_N, seed=0xD16E57):
+def signed_pool(n=POOL_N, seed=0xD16E57, lens=None):
     """n requests signed by the oracle over messages of the lengths that cross
-    SHA-256's padding and block edges, then a seeded spread of 0..700 B; one in
-    five damaged after signing (a flipped message byte, a flipped S bit, a
+    SHA-256's padding and block edges, then a seeded spread of 0..700 B (or of
+    the n lengths given); one in five damaged after signing (a flipped message byte, a flipped S bit, a
     small-order A), so a digest is owed for rejected requests too"""
     r = random.Random(seed)
     keys = [orc.keypair(bytes([k, seed & 255]) * 16) for k in range(16)]
-    lens = SPECIAL_LENS + [r.randrange(0, 701) for _ in range(n - len(SPECIAL_LENS))]
+    lens = lens or SPECIAL_LENS + [r.randrange(0, 701) for _ in range(n - len(SPECIAL_LENS))]
     sigs, pks, msgs = [], [], []
     for i, ln in enumerate(lens):
         pk, sk = keys[r.randrange(16)]
