@@ -219,6 +219,51 @@ int edv_merkle_extend_dev(uint64_t old_size, const uint8_t *d_old_hashes,
                           uint8_t *d_new_hashes, uint8_t *d_root, int device, void *stream);
 
 /*
+ * Batched append (row f-6): edv_merkle_extend that also returns what each of
+ * the n `append` calls of the reference returns (ledger/ledger.py:145-155 over
+ * ledger/compact_merkle_tree.py:155-160, called once per transaction by
+ * plenum/common/ledger.py:71-96, commitTxns), for every leaf i (0-based):
+ *   roots        n x 32 bytes: the root hash of the tree of old_size + i + 1
+ *                leaves; roots[n - 1] equals root (NULL: not wanted)
+ *   audit_paths  leaf i's audit path: the hashes of the tree of old_size + i
+ *                leaves, smallest subtree first (the reference's
+ *                reversed(hashes)), popcount(old_size + i) x 32 bytes, packed
+ *                one path after another: leaf i's starts at entry
+ *                edv_merkle_path_entries(old_size, i, ..), the whole output is
+ *                edv_merkle_path_entries(old_size, n, ..) x 32 bytes
+ *                (NULL: not wanted)
+ * Every other argument, limit, alignment rule and EDV_E_ARG case is
+ * edv_merkle_extend[_dev]'s; d_roots and d_audit_paths are hash buffers
+ * (16-byte aligned, not overlapping the inputs).  With roots and audit_paths
+ * both NULL the call is edv_merkle_extend.  n = 0 writes neither.  One more
+ * kernel after the passes, one lane per leaf: the lane folds popcount(s) - 1
+ * node hashes, s = old_size + i + 1, and gathers its path.  It reads the leaf
+ * and node hashes on the device, so they are kept there whether wanted or
+ * not: the host form stages them with its other outputs and skips the copy
+ * back, the device form puts a NULL d_leaf_hashes / d_node_hashes into context
+ * scratch, ordered across streams with the tile-root scratch.  All of it is
+ * counted in edv_context_memory out[2] and freed by edv_trim and edv_release.
+ * The packed paths of a maximal call are gigabytes: a failed allocation of the
+ * host form's staging returns EDV_E_OOM with nothing written.
+ */
+int edv_merkle_append_batch(uint64_t old_size, const uint8_t *old_hashes,
+                            const uint8_t *leaves, const uint64_t *leaf_off, uint64_t n,
+                            uint8_t *leaf_hashes, uint8_t *node_hashes,
+                            uint8_t *new_hashes, uint8_t *root,
+                            uint8_t *roots, uint8_t *audit_paths, int device);
+int edv_merkle_append_batch_dev(uint64_t old_size, const uint8_t *d_old_hashes,
+                                const uint8_t *d_leaves, const uint64_t *d_leaf_off, uint64_t leaf_base, uint64_t n,
+                                uint8_t *d_leaf_hashes, uint8_t *d_node_hashes,
+                                uint8_t *d_new_hashes, uint8_t *d_root,
+                                uint8_t *d_roots, uint8_t *d_audit_paths, int device, void *stream);
+/* Host only (no device is touched): *entries = the number of audit-path
+ * entries of the first n appends to a tree of old_size leaves, the sum of
+ * popcount(old_size + i) over i < n.  EDV_E_ARG: NULL entries, old_size + n
+ * above 2^62.  (An int result with an out-parameter, like every entry point
+ * here.) */
+int edv_merkle_path_entries(uint64_t old_size, uint64_t n, uint64_t *entries);
+
+/*
  * Pipelined submission of device-resident batches (a continuous stream of
  * client batches, e.g. one per Node prod): enqueues the batch and returns
  * without waiting.  Consecutive submissions alternate between two internal

@@ -10,3 +10,12 @@ plus batch entry points (authenticate_batch, verify_batch) that hand a whole
 client-inbox batch to the HIP kernels through the C-ABI in include/edv.h.
 """
 __version__ = "0.1.0"
+
+__all__ = ["Ledger"]
+
+
+def __getattr__(name):  # the ledger (row f-6), imported on first use
+    if name == "Ledger":
+        from .ledger import Ledger
+        return Ledger
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -686,4 +686,41 @@ int hc_merkle_extend(uint64_t old_size, const uint8_t* old_hashes, const uint8_t
   memcpy(root, rootw.data(), 32);
   return 0;
 }
+// ---- the batched append (edv_merkle.h, row f-6)
+uint64_t hc_merkle_path_entries(uint64_t old_size, uint64_t n) { return merkle_path_entries(old_size, n); }
+// edv_merkle_append_batch's signature minus `device`: hc_merkle_extend, then
+// the append kernel's lanes one after another over the hashes it wrote.
+int hc_merkle_append_batch(uint64_t old_size, const uint8_t* old_hashes, const uint8_t* leaves, const uint64_t* off,
+                           uint64_t n, uint8_t* leaf_hashes, uint8_t* node_hashes, uint8_t* new_hashes, uint8_t* root,
+                           uint8_t* roots, uint8_t* audit_paths) {
+  if (old_size > kMerkleMaxSize || n > kMerkleMaxSize || old_size + n > kMerkleMaxSize) return -1;
+  const bool per_leaf = n != 0 && (roots || audit_paths);
+  const uint64_t nodes = merkle_node_count(old_size + n) - merkle_node_count(old_size);
+  // the fold reads the leaf and node hashes whether the caller wants them or not
+  std::vector<uint8_t> lh(per_leaf && !leaf_hashes ? 32 * n : 0), nh(per_leaf && !node_hashes ? 32 * nodes + 1 : 0);
+  uint8_t* lhp = leaf_hashes ? leaf_hashes : (per_leaf ? lh.data() : nullptr);
+  uint8_t* nhp = node_hashes ? node_hashes : (per_leaf ? nh.data() : nullptr);
+  if (const int rc = hc_merkle_extend(old_size, old_hashes, leaves, off, n, lhp, nhp, new_hashes, root)) return rc;
+  if (!per_leaf) return 0;
+  const uint64_t entries = merkle_path_entries(old_size, n);
+  // exact sizes, here and below: a lane reading or storing a hash too far is ASan's to see
+  std::vector<uint32_t> oldw(8 * size_t(popc64(old_size))), leafw(8 * n), nodew(8 * nodes);
+  std::vector<uint32_t> rootsw(roots ? 8 * n : 0), pathsw(audit_paths ? 8 * entries : 0);
+  if (old_size) memcpy(oldw.data(), old_hashes, 32 * size_t(popc64(old_size)));
+  memcpy(leafw.data(), lhp, 32 * n);
+  if (nodes) memcpy(nodew.data(), nhp, 32 * nodes);
+  MerkleAppend a;
+  a.old_size = old_size;
+  a.n = n;
+  a.path_base = merkle_popc_prefix(old_size);
+  a.old_hashes = oldw.data();
+  a.leaf_hashes = leafw.data();
+  a.node_hashes = nodew.data();
+  a.roots = roots ? rootsw.data() : nullptr;
+  a.paths = audit_paths ? pathsw.data() : nullptr;
+  for (uint64_t i = 0; i < n; i++) merkle_append_leaf(a, i);
+  if (roots) memcpy(roots, rootsw.data(), 32 * n);
+  if (audit_paths && entries) memcpy(audit_paths, pathsw.data(), 32 * entries);
+  return 0;
+}
 }

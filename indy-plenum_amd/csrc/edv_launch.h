@@ -43,5 +43,9 @@ hipError_t launch_merkle_pass_kernel(hipStream_t s, const MerklePass& a, const u
                                      uint64_t leaf_base);
 hipError_t launch_merkle_finish_kernel(hipStream_t s, uint64_t old_size, uint64_t new_size, const uint32_t* old_hashes,
                                        uint32_t* new_hashes, uint32_t* root);
+// per-leaf roots and audit paths (MerkleAppend: edv_merkle.h), after the passes
+// on the same stream; no launch for n = 0 or with neither output wanted
+struct MerkleAppend;
+hipError_t launch_merkle_append_kernel(hipStream_t s, const MerkleAppend& a);
 
 }  // namespace edv

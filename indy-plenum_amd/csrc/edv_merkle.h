@@ -1,5 +1,6 @@
 // edv_merkle.h -- extending a compact RFC 6962 Merkle tree by a batch of leaves
-// (SURVEY.md section 8f row f-5).
+// (SURVEY.md section 8f row f-5), and what each of the appends returns: the
+// root after it and its audit path (row f-6, at the end of this file).
 //
 // Replaces, per batch of transactions:
 //   ledger/ledger.py:145-148              Ledger._addToTree (one append per txn)
@@ -295,6 +296,97 @@ EDV_HD void merkle_finish(uint64_t old_size, uint64_t new_size, const uint32_t* 
   uint32_t R[8];
   merkle_fold(R, new_hashes, popc64(new_size));
   merkle_store_hash(root, R);
+}
+
+// ---- per-leaf roots and audit paths (row f-6: what n calls of `append` return)
+// Leaf i (0-based) of a call extending `old` by n gives the tree of size
+// s = old + i + 1.  The entry of hashes(s) for set bit b is block
+// k = (s >> b) - 1 at height b.  If that block ends at or before `old`
+// ((k + 1) << b <= old) then old >> b == s >> b, so it is the old tree's entry
+// for the same bit, at the same index; otherwise the call made it: a leaf hash
+// (b = 0) or a node at its node-store position.  Nothing is hashed twice: the
+// passes have written every entry before the append kernel reads it.
+struct MerkleAppend {
+  uint64_t old_size, n;
+  uint64_t path_base;           // merkle_popc_prefix(old_size)
+  const uint32_t* old_hashes;   // popcount(old_size) entries
+  const uint32_t* leaf_hashes;  // the call's n leaf hashes
+  const uint32_t* node_hashes;  // the call's nodes, node-store order
+  uint32_t* roots;              // root after leaf i at 8 i, or null
+  uint32_t* paths;              // packed audit paths, or null
+};
+
+// P(x) = sum of popcount(t) over t < x, modulo 2^64 (x <= 2^62; P(2^62) is
+// above 2^64, differences over one call are not): bit b is set in
+// (x >> (b + 1)) 2^b numbers below x, plus the part of x's last period of
+// 2^(b + 1) past its first half.
+EDV_HD uint64_t merkle_popc_prefix(uint64_t x) {
+  uint64_t p = 0;
+#pragma unroll 1
+  for (int b = 0; b < 63 && (x >> b) != 0; b++) {
+    const uint64_t half = uint64_t(1) << b;
+    const uint64_t rem = x & ((half << 1) - 1);
+    p += ((x >> (b + 1)) << b) + (rem > half ? rem - half : 0);
+  }
+  return p;
+}
+// audit-path entries of the first n appends to a tree of old_size leaves
+// (leaf i's path has popcount(old_size + i) entries)
+EDV_HD uint64_t merkle_path_entries(uint64_t old_size, uint64_t n) {
+  return merkle_popc_prefix(old_size + n) - merkle_popc_prefix(old_size);
+}
+// the entry of hashes(s) for set bit b of s, old_size <= s <= old_size + n
+EDV_HD const uint32_t* merkle_entry(const MerkleAppend& a, uint64_t s, int b) {
+  const uint64_t k = (s >> b) - 1;
+  if (((k + 1) << b) <= a.old_size) return a.old_hashes + 8 * merkle_hashes_index(a.old_size, b);
+  if (b == 0) return a.leaf_hashes + 8 * (k - a.old_size);
+  return a.node_hashes + 8 * (merkle_store_pos(b, k) - 1 - merkle_node_count(a.old_size));
+}
+EDV_HD void merkle_copy_hash(uint32_t* dst, const uint32_t* src) {  // both 16-byte aligned on the device
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint4* p = reinterpret_cast<const uint4*>(src);
+  const uint4 x = p[0], y = p[1];
+  uint4* q = reinterpret_cast<uint4*>(dst);
+  q[0] = x;
+  q[1] = y;
+#else
+  for (int w = 0; w < 8; w++) dst[w] = src[w];
+#endif
+}
+// Leaf i of the call, i < a.n: the root of the tree after it (merkle_fold's
+// order over the entries of hashes(s): from the lowest set bit up) and its
+// audit path (the entries of hashes(s - 1), lowest bit first, at entry
+// P(old + i) - P(old) of the packed output).
+EDV_HD void merkle_append_leaf(const MerkleAppend& a, uint64_t i) {
+  const uint64_t s = a.old_size + i + 1;
+  if (a.roots) {
+    uint64_t bits = s;
+    int b = __builtin_ctzll(bits);
+    uint32_t acc[8];
+    merkle_load_hash(acc, merkle_entry(a, s, b));
+    bits &= bits - 1;
+#pragma unroll 1
+    while (bits) {
+      b = __builtin_ctzll(bits);
+      bits &= bits - 1;
+      uint32_t l[8], r[8];
+      merkle_load_hash(l, merkle_entry(a, s, b));
+      for (int w = 0; w < 8; w++) r[w] = acc[w];
+      merkle_node_hash(acc, l, r);
+    }
+    merkle_store_hash(a.roots + 8 * i, acc);
+  }
+  if (a.paths) {
+    uint32_t* out = a.paths + 8 * (merkle_popc_prefix(s - 1) - a.path_base);
+    uint64_t bits = s - 1;
+#pragma unroll 1
+    while (bits) {
+      const int b = __builtin_ctzll(bits);
+      bits &= bits - 1;
+      merkle_copy_hash(out, merkle_entry(a, s - 1, b));
+      out += 8;
+    }
+  }
 }
 
 }  // namespace edv

@@ -5,7 +5,8 @@
 // pass before wrote), then kMerkleLogT levels are reduced in two LDS buffers
 // used in turn, one __syncthreads() per level.  Workgroups never talk to each
 // other: a pass reads what the pass before wrote, and passes are separate
-// launches on one stream.
+// launches on one stream.  The batched append (row f-6) adds one kernel after
+// them: one lane per new leaf, the root after it and its audit path.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -47,6 +48,16 @@ __global__ __launch_bounds__(64) void edv_merkle_finish_kernel(uint64_t old_size
   if (blockIdx.x == 0 && threadIdx.x == 0) merkle_finish(old_size, new_size, old_hashes, new_hashes, root);
 }
 
+// Row f-6: one lane per new leaf folds the root of the tree after it and
+// copies its audit path (merkle_append_leaf), from the leaf and node hashes the
+// passes before it on the stream have written.  No LDS, no lane talks to
+// another; lanes of a wave differ in trip count through the low bits of s.
+constexpr int kMerkleAppendLanes = 64;
+__global__ __launch_bounds__(kMerkleAppendLanes) void edv_merkle_append_kernel(MerkleAppend a) {
+  const uint64_t i = uint64_t(blockIdx.x) * kMerkleAppendLanes + threadIdx.x;
+  if (i < a.n) merkle_append_leaf(a, i);
+}
+
 }  // namespace
 
 namespace edv {
@@ -66,6 +77,13 @@ hipError_t launch_merkle_pass_kernel(hipStream_t s, const MerklePass& a, const u
 hipError_t launch_merkle_finish_kernel(hipStream_t s, uint64_t old_size, uint64_t new_size, const uint32_t* old_hashes,
                                        uint32_t* new_hashes, uint32_t* root) {
   edv_merkle_finish_kernel<<<dim3(1), dim3(64), 0, s>>>(old_size, new_size, old_hashes, new_hashes, root);
+  return hipGetLastError();
+}
+
+hipError_t launch_merkle_append_kernel(hipStream_t s, const MerkleAppend& a) {
+  if (a.n == 0 || (!a.roots && !a.paths)) return hipSuccess;
+  const uint64_t blocks = (a.n + kMerkleAppendLanes - 1) / kMerkleAppendLanes;
+  edv_merkle_append_kernel<<<dim3(unsigned(blocks)), dim3(kMerkleAppendLanes), 0, s>>>(a);
   return hipGetLastError();
 }
 

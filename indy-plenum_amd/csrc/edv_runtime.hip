@@ -238,9 +238,16 @@ struct DevCtx {
   // and waited for by the next user (as st_done for the verify scratch).  The
   // other buffers are the host form's staging, its alone while it holds mu.
   DevBuf mk_roots, mk_leaves, mk_off, mk_hashes, mk_leafh, mk_nodeh;
+  // batched append (edv_merkle_append_batch[_dev]): mk_fleafh / mk_fnodeh hold
+  // the leaf and node hashes the fold reads when the device form's caller did
+  // not ask for them (scratch, ordered by mk_done like mk_roots; the host form
+  // uses its own staging mk_leafh / mk_nodeh); mk_aroots / mk_paths are
+  // the host form's staging of the per-leaf roots and the packed audit paths
+  DevBuf mk_fleafh, mk_fnodeh, mk_aroots, mk_paths;
   hipEvent_t mk_done = nullptr;
   uint64_t mk_bytes() const {
-    return mk_roots.cap + mk_leaves.cap + mk_off.cap + mk_hashes.cap + mk_leafh.cap + mk_nodeh.cap;
+    return mk_roots.cap + mk_leaves.cap + mk_off.cap + mk_hashes.cap + mk_leafh.cap + mk_nodeh.cap +
+           mk_fleafh.cap + mk_fnodeh.cap + mk_aroots.cap + mk_paths.cap;
   }
 #ifdef EDV_MEASUREMENT_API
   int64_t inject_fail = -1;        // edv_test_fail_async (libedv_measure.so only)
@@ -1283,17 +1290,28 @@ int run_digest_shard(DevCtx& c, const uint8_t* msgs, const uint64_t* off, uint64
 // The tile roots go through c.mk_roots, grown here after its queued users are
 // done; launches on different streams are ordered on it by c.mk_done.  Caller
 // holds c.mu.
+// d_aroots / d_paths (either may be null): the per-leaf roots and packed audit
+// paths of the batched append, by one more kernel after the finish.  It reads
+// the call's leaf and node hashes, so where d_leafh / d_nodeh is null they go
+// to c.mk_fleafh / c.mk_fnodeh, scratch under the same event.
 int launch_merkle(DevCtx& c, uint64_t old_size, const uint8_t* d_old, const uint8_t* d_leaves, const uint64_t* d_off,
                   uint64_t leaf_base, uint64_t n, uint8_t* d_leafh, uint8_t* d_nodeh, uint8_t* d_new, uint8_t* d_root,
-                  hipStream_t s) {
+                  hipStream_t s, uint8_t* d_aroots = nullptr, uint8_t* d_paths = nullptr) {
   const uint64_t new_size = old_size + n;
   if (!c.mk_done) HIPOK(hipEventCreateWithFlags(&c.mk_done, hipEventDisableTiming), "event");
+  const bool per_leaf = n != 0 && (d_aroots || d_paths);
+  const uint64_t nodes = merkle_node_count(new_size) - merkle_node_count(old_size);
   const uint64_t need = 32 * merkle_scratch_hashes(old_size, new_size);
-  if (need > c.mk_roots.cap) {
+  const uint64_t need_leafh = per_leaf && !d_leafh ? 32 * n : 0;
+  const uint64_t need_nodeh = per_leaf && !d_nodeh ? 32 * nodes : 0;
+  if (need > c.mk_roots.cap || need_leafh > c.mk_fleafh.cap || need_nodeh > c.mk_fnodeh.cap) {
     HIPOK(hipEventSynchronize(c.mk_done), "merkle scratch sync");
-    if (c.mk_roots.ensure(need)) return EDV_E_OOM;
+    if (c.mk_roots.ensure(need) || c.mk_fleafh.ensure(need_leafh) || c.mk_fnodeh.ensure(need_nodeh)) return EDV_E_OOM;
   }
-  if (need) HIPOK(hipStreamWaitEvent(s, c.mk_done, 0), "wait merkle scratch");
+  const bool scratch = need || need_leafh || need_nodeh;
+  if (scratch) HIPOK(hipStreamWaitEvent(s, c.mk_done, 0), "wait merkle scratch");
+  if (need_leafh) d_leafh = static_cast<uint8_t*>(c.mk_fleafh.p);
+  if (need_nodeh) d_nodeh = static_cast<uint8_t*>(c.mk_fnodeh.p);
   MerklePass a;
   a.old_size = old_size;
   a.new_size = new_size;
@@ -1315,22 +1333,43 @@ int launch_merkle(DevCtx& c, uint64_t old_size, const uint8_t* d_old, const uint
   HIPOK(launch_merkle_finish_kernel(s, old_size, new_size, a.old_hashes, a.new_hashes,
                                     reinterpret_cast<uint32_t*>(d_root)),
         "merkle finish launch");
-  if (need) HIPOK(hipEventRecord(c.mk_done, s), "record merkle scratch");
+  if (per_leaf) {
+    MerkleAppend ap;
+    ap.old_size = old_size;
+    ap.n = n;
+    ap.path_base = merkle_popc_prefix(old_size);
+    ap.old_hashes = a.old_hashes;
+    ap.leaf_hashes = a.leaf_out;
+    ap.node_hashes = a.node_out;
+    ap.roots = reinterpret_cast<uint32_t*>(d_aroots);
+    ap.paths = reinterpret_cast<uint32_t*>(d_paths);
+    HIPOK(launch_merkle_append_kernel(s, ap), "merkle append launch");
+  }
+  if (scratch) HIPOK(hipEventRecord(c.mk_done, s), "record merkle scratch");
   return 0;
 }
 
 // The host form: staged like run_digest_shard, in buffers of its own; copies
-// back only the outputs asked for.  Caller holds c.mu.
+// back only the outputs asked for (roots / audit_paths: the batched append's,
+// null from edv_merkle_extend).  The per-leaf fold reads the leaf and node
+// hashes on the device, so with roots or audit_paths wanted they are staged in
+// mk_leafh / mk_nodeh whether the caller asked for them or not, and only the
+// copy back is skipped (mk_fleafh / mk_fnodeh are the device form's alone).
+// Caller holds c.mu.
 int run_merkle_host(DevCtx& c, uint64_t old_size, const uint8_t* old_hashes, const uint8_t* leaves, const uint64_t* off,
-                    uint64_t n, uint8_t* leaf_hashes, uint8_t* node_hashes, uint8_t* new_hashes, uint8_t* root) {
+                    uint64_t n, uint8_t* leaf_hashes, uint8_t* node_hashes, uint8_t* new_hashes, uint8_t* root,
+                    uint8_t* roots = nullptr, uint8_t* audit_paths = nullptr) {
   const uint64_t new_size = old_size + n;
   const uint64_t nold = uint64_t(popc64(old_size)), nnew = uint64_t(popc64(new_size));
   const uint64_t nodes = merkle_node_count(new_size) - merkle_node_count(old_size);
   const uint64_t mbase = n ? off[0] : 0, mbytes = n ? off[n] - off[0] : 0;
+  const uint64_t pbytes = audit_paths ? 32 * merkle_path_entries(old_size, n) : 0;
+  const bool per_leaf = n != 0 && (roots || audit_paths);
   // mk_hashes: old entries | new entries | root, 32 bytes each
   if (c.mk_leaves.ensure(mbytes + 64) || c.mk_off.ensure((n + 1) * 8) ||
-      c.mk_hashes.ensure(32 * (2 * kMerkleMaxHashes + 2)) || (leaf_hashes && c.mk_leafh.ensure(32 * n)) ||
-      (node_hashes && c.mk_nodeh.ensure(32 * nodes)))
+      c.mk_hashes.ensure(32 * (2 * kMerkleMaxHashes + 2)) || ((leaf_hashes || per_leaf) && c.mk_leafh.ensure(32 * n)) ||
+      ((node_hashes || per_leaf) && c.mk_nodeh.ensure(32 * nodes)) || (roots && c.mk_aroots.ensure(32 * n)) ||
+      c.mk_paths.ensure(pbytes))
     return EDV_E_OOM;
   const hipStream_t s = c.stream;
   uint8_t* d_old = static_cast<uint8_t*>(c.mk_hashes.p);
@@ -1339,14 +1378,18 @@ int run_merkle_host(DevCtx& c, uint64_t old_size, const uint8_t* old_hashes, con
   if (mbytes) HIPOK(hipMemcpyAsync(c.mk_leaves.p, leaves + mbase, mbytes, hipMemcpyHostToDevice, s), "h2d leaves");
   if (n) HIPOK(hipMemcpyAsync(c.mk_off.p, off, (n + 1) * 8, hipMemcpyHostToDevice, s), "h2d leaf_off");
   if (nold) HIPOK(hipMemcpyAsync(d_old, old_hashes, 32 * nold, hipMemcpyHostToDevice, s), "h2d old hashes");
-  uint8_t* d_leafh = leaf_hashes && n ? static_cast<uint8_t*>(c.mk_leafh.p) : nullptr;
-  uint8_t* d_nodeh = node_hashes && nodes ? static_cast<uint8_t*>(c.mk_nodeh.p) : nullptr;
+  uint8_t* d_leafh = (leaf_hashes || per_leaf) && n ? static_cast<uint8_t*>(c.mk_leafh.p) : nullptr;
+  uint8_t* d_nodeh = (node_hashes || per_leaf) && nodes ? static_cast<uint8_t*>(c.mk_nodeh.p) : nullptr;
+  uint8_t* d_aroots = roots && n ? static_cast<uint8_t*>(c.mk_aroots.p) : nullptr;
+  uint8_t* d_paths = pbytes ? static_cast<uint8_t*>(c.mk_paths.p) : nullptr;
   int err;
   if ((err = launch_merkle(c, old_size, d_old, static_cast<uint8_t*>(c.mk_leaves.p), static_cast<uint64_t*>(c.mk_off.p),
-                           mbase, n, d_leafh, d_nodeh, d_new, d_root, s)))
+                           mbase, n, d_leafh, d_nodeh, d_new, d_root, s, d_aroots, d_paths)))
     return err;
-  if (d_leafh) HIPOK(hipMemcpyAsync(leaf_hashes, d_leafh, 32 * n, hipMemcpyDeviceToHost, s), "d2h leaf hashes");
-  if (d_nodeh) HIPOK(hipMemcpyAsync(node_hashes, d_nodeh, 32 * nodes, hipMemcpyDeviceToHost, s), "d2h node hashes");
+  if (d_aroots) HIPOK(hipMemcpyAsync(roots, d_aroots, 32 * n, hipMemcpyDeviceToHost, s), "d2h roots");
+  if (d_paths) HIPOK(hipMemcpyAsync(audit_paths, d_paths, pbytes, hipMemcpyDeviceToHost, s), "d2h audit paths");
+  if (leaf_hashes && d_leafh) HIPOK(hipMemcpyAsync(leaf_hashes, d_leafh, 32 * n, hipMemcpyDeviceToHost, s), "d2h leaf hashes");
+  if (node_hashes && d_nodeh) HIPOK(hipMemcpyAsync(node_hashes, d_nodeh, 32 * nodes, hipMemcpyDeviceToHost, s), "d2h node hashes");
   if (nnew) HIPOK(hipMemcpyAsync(new_hashes, d_new, 32 * nnew, hipMemcpyDeviceToHost, s), "d2h new hashes");
   HIPOK(hipMemcpyAsync(root, d_root, 32, hipMemcpyDeviceToHost, s), "d2h root");
   HIPOK(hipStreamSynchronize(s), "stream sync");
@@ -1706,6 +1749,10 @@ void trim_buffers(DevCtx& c, uint64_t keep) {
   dev(c.mk_hashes, k ? 32 * (2 * kMerkleMaxHashes + 2) : 0);
   dev(c.mk_leafh, 32 * k);
   dev(c.mk_nodeh, 32 * k);
+  dev(c.mk_fleafh, 32 * k);
+  dev(c.mk_fnodeh, 32 * k);
+  dev(c.mk_aroots, 32 * k);
+  dev(c.mk_paths, 32 * kMerkleMaxHashes * k);  // a path is at most kMerkleMaxHashes entries
   for (auto& a : c.as) {
     set(a.cb);
     dev(a.sigs, t.sigs);
@@ -2131,6 +2178,13 @@ int edv_sha256_batch_dev(const uint8_t* d_msgs, const uint64_t* d_msg_off, uint6
 int edv_merkle_extend(uint64_t old_size, const uint8_t* old_hashes, const uint8_t* leaves, const uint64_t* leaf_off,
                       uint64_t n, uint8_t* leaf_hashes, uint8_t* node_hashes, uint8_t* new_hashes, uint8_t* root,
                       int device) {
+  return edv_merkle_append_batch(old_size, old_hashes, leaves, leaf_off, n, leaf_hashes, node_hashes, new_hashes, root,
+                                 nullptr, nullptr, device);
+}
+
+int edv_merkle_append_batch(uint64_t old_size, const uint8_t* old_hashes, const uint8_t* leaves,
+                            const uint64_t* leaf_off, uint64_t n, uint8_t* leaf_hashes, uint8_t* node_hashes,
+                            uint8_t* new_hashes, uint8_t* root, uint8_t* roots, uint8_t* audit_paths, int device) {
   g_err.clear();
   if (n > EDV_MERKLE_MAX_LEAVES) return set_err(EDV_E_ARG, "merkle: more than EDV_MERKLE_MAX_LEAVES leaves");
   if (old_size > kMerkleMaxSize || old_size + n > kMerkleMaxSize) return set_err(EDV_E_ARG, "merkle: tree size above 2^62");
@@ -2144,12 +2198,30 @@ int edv_merkle_extend(uint64_t old_size, const uint8_t* old_hashes, const uint8_
   }
   CtxLock cl(device);
   if (cl.err) return cl.err;
-  return run_merkle_host(*cl.c, old_size, old_hashes, leaves, leaf_off, n, leaf_hashes, node_hashes, new_hashes, root);
+  return run_merkle_host(*cl.c, old_size, old_hashes, leaves, leaf_off, n, leaf_hashes, node_hashes, new_hashes, root,
+                         roots, audit_paths);
+}
+
+int edv_merkle_path_entries(uint64_t old_size, uint64_t n, uint64_t* entries) {
+  g_err.clear();
+  if (!entries) return set_err(EDV_E_ARG, "merkle: null entries");
+  if (old_size > kMerkleMaxSize || n > kMerkleMaxSize || old_size + n > kMerkleMaxSize)
+    return set_err(EDV_E_ARG, "merkle: tree size above 2^62");
+  *entries = merkle_path_entries(old_size, n);
+  return 0;
 }
 
 int edv_merkle_extend_dev(uint64_t old_size, const uint8_t* d_old_hashes, const uint8_t* d_leaves,
                           const uint64_t* d_leaf_off, uint64_t leaf_base, uint64_t n, uint8_t* d_leaf_hashes,
                           uint8_t* d_node_hashes, uint8_t* d_new_hashes, uint8_t* d_root, int device, void* stream) {
+  return edv_merkle_append_batch_dev(old_size, d_old_hashes, d_leaves, d_leaf_off, leaf_base, n, d_leaf_hashes,
+                                     d_node_hashes, d_new_hashes, d_root, nullptr, nullptr, device, stream);
+}
+
+int edv_merkle_append_batch_dev(uint64_t old_size, const uint8_t* d_old_hashes, const uint8_t* d_leaves,
+                                const uint64_t* d_leaf_off, uint64_t leaf_base, uint64_t n, uint8_t* d_leaf_hashes,
+                                uint8_t* d_node_hashes, uint8_t* d_new_hashes, uint8_t* d_root, uint8_t* d_roots,
+                                uint8_t* d_audit_paths, int device, void* stream) {
   g_err.clear();
   // before anything reaches the GPU: the kernels read the offsets as 64-bit
   // words and read and store every hash as two 16-byte vectors
@@ -2161,14 +2233,15 @@ int edv_merkle_extend_dev(uint64_t old_size, const uint8_t* d_old_hashes, const 
   if (reinterpret_cast<uintptr_t>(d_leaf_off) & 7) return set_err(EDV_E_ARG, "merkle: d_leaf_off must be 8-byte aligned");
   for (const uint8_t* p : {d_old_hashes, static_cast<const uint8_t*>(d_leaf_hashes),
                            static_cast<const uint8_t*>(d_node_hashes), static_cast<const uint8_t*>(d_new_hashes),
-                           static_cast<const uint8_t*>(d_root)})
+                           static_cast<const uint8_t*>(d_root), static_cast<const uint8_t*>(d_roots),
+                           static_cast<const uint8_t*>(d_audit_paths)})
     if (reinterpret_cast<uintptr_t>(p) & 15) return set_err(EDV_E_ARG, "merkle: hash buffers must be 16-byte aligned");
   CtxLock cl(device);
   if (cl.err) return cl.err;
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : cl.c->stream;
   int err;
   if ((err = launch_merkle(*cl.c, old_size, d_old_hashes, d_leaves, d_leaf_off, leaf_base, n, d_leaf_hashes,
-                           d_node_hashes, d_new_hashes, d_root, s)))
+                           d_node_hashes, d_new_hashes, d_root, s, d_roots, d_audit_paths)))
     return err;
   if (!stream) HIPOK(hipStreamSynchronize(s), "stream sync");
   return 0;

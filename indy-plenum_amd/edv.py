@@ -93,6 +93,12 @@ def lib():
         h.edv_merkle_extend.restype = ctypes.c_int
         h.edv_merkle_extend_dev.argtypes = [u64, vp, vp, vp, u64, u64, vp, vp, vp, vp, ctypes.c_int, vp]
         h.edv_merkle_extend_dev.restype = ctypes.c_int
+        h.edv_merkle_append_batch.argtypes = [u64, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, ctypes.c_int]
+        h.edv_merkle_append_batch.restype = ctypes.c_int
+        h.edv_merkle_append_batch_dev.argtypes = [u64, vp, vp, vp, u64, u64, vp, vp, vp, vp, vp, vp, ctypes.c_int, vp]
+        h.edv_merkle_append_batch_dev.restype = ctypes.c_int
+        h.edv_merkle_path_entries.argtypes = [u64, u64, ctypes.POINTER(u64)]
+        h.edv_merkle_path_entries.restype = ctypes.c_int
         h.edv_verify_batch_dev_flags.argtypes = [vp, vp, vp, vp, u64, u64, vp, ctypes.c_int, vp, ctypes.c_uint32]
         h.edv_verify_batch_dev_flags.restype = ctypes.c_int
         h.edv_verify_batch_dev_pipelined.argtypes = [vp, vp, vp, vp, u64, u64, vp, ctypes.c_int, ctypes.c_uint32]
@@ -463,16 +469,10 @@ def merkle_node_span(old_size: int, n: int) -> int:
     return (new - bin(new).count("1")) - (old_size - bin(old_size).count("1"))
 
 
-def merkle_extend(old_size: int, old_hashes, leaves, offsets, want_leaf_hashes=True, want_node_hashes=True,
-                  device: int = 0):
-    """Extend the compact RFC 6962 Merkle tree (old_size, old_hashes) by the n
-    leaves laid out as msgs / offsets everywhere else (edv_merkle_extend, row f-5).
-
-    old_hashes: popcount(old_size) x 32 bytes (bytes or uint8 array), largest
-    subtree first.  Returns (leaf_hashes, node_hashes, new_hashes, root):
-    (n, 32), (nodes, 32) and (popcount(new), 32) uint8 arrays and 32 bytes;
-    leaf_hashes / node_hashes are None when not wanted.  Bit-exact with n
-    successive appends of the reference's CompactMerkleTree."""
+def _merkle_call(old_size, old_hashes, leaves, offsets, want_leaf_hashes, want_node_hashes):
+    """The checked inputs and the zeroed outputs that merkle_extend and
+    merkle_append_batch share: (old_size, n, the C call's first five arguments,
+    leaf_h, node_h, new_h, root)."""
     off = np.ascontiguousarray(offsets, dtype=np.uint64)
     if off.ndim != 1 or len(off) < 1:
         raise ValueError("offsets must hold n + 1 entries")
@@ -499,11 +499,28 @@ def merkle_extend(old_size: int, old_hashes, leaves, offsets, want_leaf_hashes=T
     node_h = np.zeros((merkle_node_span(old_size, n), 32), dtype=np.uint8) if want_node_hashes else None
     new_h = np.zeros((bin(new_size).count("1"), 32), dtype=np.uint8)
     root = np.zeros(32, dtype=np.uint8)
-    _check(lib().edv_merkle_extend(old_size, old_hashes.ctypes.data if old_hashes.nbytes else None,
-                                   leaves.ctypes.data, off.ctypes.data, n,
-                                   None if leaf_h is None else leaf_h.ctypes.data,
-                                   None if node_h is None else node_h.ctypes.data,
-                                   new_h.ctypes.data, root.ctypes.data, device))
+    head = (old_size, old_hashes.ctypes.data if old_hashes.nbytes else None, leaves.ctypes.data, off.ctypes.data, n)
+    # old_hashes, leaves and off are returned so that they outlive the call
+    return old_size, n, head, (old_hashes, leaves, off), leaf_h, node_h, new_h, root
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def merkle_extend(old_size: int, old_hashes, leaves, offsets, want_leaf_hashes=True, want_node_hashes=True,
+                  device: int = 0):
+    """Extend the compact RFC 6962 Merkle tree (old_size, old_hashes) by the n
+    leaves laid out as msgs / offsets everywhere else (edv_merkle_extend, row f-5).
+
+    old_hashes: popcount(old_size) x 32 bytes (bytes or uint8 array), largest
+    subtree first.  Returns (leaf_hashes, node_hashes, new_hashes, root):
+    (n, 32), (nodes, 32) and (popcount(new), 32) uint8 arrays and 32 bytes;
+    leaf_hashes / node_hashes are None when not wanted.  Bit-exact with n
+    successive appends of the reference's CompactMerkleTree."""
+    _, _, head, _keep, leaf_h, node_h, new_h, root = _merkle_call(old_size, old_hashes, leaves, offsets,
+                                                                  want_leaf_hashes, want_node_hashes)
+    _check(lib().edv_merkle_extend(*head, _ptr(leaf_h), _ptr(node_h), new_h.ctypes.data, root.ctypes.data, device))
     return leaf_h, node_h, new_h, root.tobytes()
 
 
@@ -512,6 +529,43 @@ def merkle_extend_device(old_size, d_old_hashes, d_leaves, d_off, n, d_leaf_hash
     """Device-resident form (pointers are ints, None = NULL); async on `stream` if given."""
     _check(lib().edv_merkle_extend_dev(old_size, d_old_hashes, d_leaves, d_off, leaf_base, n, d_leaf_hashes,
                                        d_node_hashes, d_new_hashes, d_root, device, stream))
+
+
+def merkle_path_entries(old_size: int, n: int) -> int:
+    """Audit-path entries of the first n appends to a tree of old_size leaves:
+    the sum of popcount(old_size + i) over i < n (edv_merkle_path_entries; no
+    device is touched).  Leaf i's path starts at entry merkle_path_entries(old_size, i)."""
+    out = ctypes.c_uint64(0)
+    _check(lib().edv_merkle_path_entries(old_size, n, ctypes.byref(out)))
+    return int(out.value)
+
+
+def merkle_append_batch(old_size: int, old_hashes, leaves, offsets, want_roots=True, want_audit_paths=True,
+                        want_leaf_hashes=True, want_node_hashes=True, device: int = 0):
+    """merkle_extend that also returns what each of the n appends returns
+    (edv_merkle_append_batch, row f-6).
+
+    Returns (leaf_hashes, node_hashes, new_hashes, root, roots, audit_paths):
+    the first four as merkle_extend; roots is (n, 32), the root after leaf i;
+    audit_paths is (merkle_path_entries(old_size, n), 32), the paths packed one
+    after another, leaf i's being the popcount(old_size + i) rows from
+    merkle_path_entries(old_size, i) on (smallest subtree first).  Outputs not
+    wanted are None."""
+    old_size, n, head, _keep, leaf_h, node_h, new_h, root = _merkle_call(old_size, old_hashes, leaves, offsets,
+                                                                         want_leaf_hashes, want_node_hashes)
+    roots = np.zeros((n, 32), dtype=np.uint8) if want_roots else None
+    paths = np.zeros((merkle_path_entries(old_size, n), 32), dtype=np.uint8) if want_audit_paths else None
+    _check(lib().edv_merkle_append_batch(*head, _ptr(leaf_h), _ptr(node_h), new_h.ctypes.data, root.ctypes.data,
+                                         _ptr(roots), _ptr(paths), device))
+    return leaf_h, node_h, new_h, root.tobytes(), roots, paths
+
+
+def merkle_append_batch_device(old_size, d_old_hashes, d_leaves, d_off, n, d_leaf_hashes, d_node_hashes, d_new_hashes,
+                               d_root, d_roots, d_audit_paths, device=0, leaf_base=0, stream=None):
+    """Device-resident form (pointers are ints, None = NULL); async on `stream` if given."""
+    _check(lib().edv_merkle_append_batch_dev(old_size, d_old_hashes, d_leaves, d_off, leaf_base, n, d_leaf_hashes,
+                                             d_node_hashes, d_new_hashes, d_root, d_roots, d_audit_paths, device,
+                                             stream))
 
 
 def verify_detached_batch(items, device_mask: int = 0):

@@ -1,0 +1,200 @@
+"""The ledger over the compact Merkle tree, with a 3PC batch committed in one
+device call.
+
+Same names, call shapes and return values as the reference's two Ledger
+classes, written from their semantics:
+
+  ledger/ledger.py:116-158                add / append -> seqNo, rootHash, auditPath
+  ledger/ledger.py:95-114                 recoverTreeFromTxnLog / recoverTreeFromHashStore
+  ledger/ledger.py:197-206                merkleInfo
+  plenum/common/ledger.py:34-53           appendTxns (uncommittedTree, uncommittedRootHash)
+  plenum/common/ledger.py:71-96           commitTxns: txn.update(self.append(txn)) per txn
+  plenum/common/ledger.py:98-137          discardTxns, treeWithAppliedTxns
+
+commitTxns(count) is one CompactMerkleTree.append_batch call
+(edv_merkle_append_batch from merkle.MIN_DEVICE_APPEND_LEAVES transactions
+on): every committed transaction still gets its own rootHash and auditPath.
+The transaction log is a list in memory; it holds each transaction as it was
+when it was hashed, a copy taken before the committed transaction is updated
+with its Merkle info (the reference logs the serialization made before the
+update), so recovery from the log hashes what was hashed and getBySeqNo never
+shows rootHash / auditPath.  Transaction metadata stays out: the
+class never looks inside a transaction, it only `update`s the committed ones
+(so neither append_txns_metadata nor appendTxns' seq-no check is here).
+"""
+from copy import copy
+
+from . import base58
+from .merkle import CompactMerkleTree, ConsistencyVerificationFailed
+
+
+def _bytes_as_they_are(txn):
+    return txn.encode() if isinstance(txn, str) else bytes(txn)
+
+
+class Ledger:
+    def __init__(self, tree=None, serialize_for_tree=None, transactionLog=None, on_device=None, device=0):
+        """serialize_for_tree: transaction -> the bytes the tree hashes (default:
+        the transaction is those bytes).  transactionLog: the committed
+        transactions so far (a list; default none).  on_device: passed to the
+        tree's extend / append_batch (None: by batch size)."""
+        self.tree = tree if tree is not None else CompactMerkleTree()
+        self.serialize_for_tree = serialize_for_tree or _bytes_as_they_are
+        self.on_device = on_device
+        self.device = device
+        self._transactionLog = list(transactionLog) if transactionLog is not None else []
+        self.seqNo = 0
+        self.reset_uncommitted()
+        self.recoverTree()
+
+    # ---- recovery
+    def recoverTree(self):
+        """From the hash store if it has leaves and agrees with the log, else from the log."""
+        if self.tree.leafCount == 0:
+            self.recoverTreeFromTxnLog()
+            return
+        try:
+            self.recoverTreeFromHashStore()
+        except ConsistencyVerificationFailed:
+            self.recoverTreeFromTxnLog()
+
+    def recoverTreeFromTxnLog(self):
+        """The tree again from the whole log: one extend."""
+        self.tree.reset()
+        self.seqNo = 0
+        if self._transactionLog:
+            self.tree.extend([self.serialize_for_tree(t) for t in self._transactionLog], on_device=self.on_device,
+                             device=self.device)
+        self.seqNo = self.tree.tree_size
+
+    def recoverTreeFromHashStore(self):
+        treeSize = self.tree.leafCount
+        self.seqNo = treeSize
+        hashes = list(reversed(self.tree.inclusion_proof(treeSize, treeSize + 1)))
+        self.tree._update(treeSize, hashes)
+        self.tree.verify_consistency(len(self._transactionLog))
+
+    # ---- committed transactions
+    def add(self, txn):
+        """One transaction into the log and the tree; its seqNo, the root hash
+        after it and its audit path."""
+        audit_path = self.tree.append(self.serialize_for_tree(txn))
+        self._transactionLog.append(copy(txn))  # the caller goes on to update its own object
+        self.seqNo += 1
+        return {"seqNo": self.seqNo,
+                "rootHash": self.hashToStr(self.tree.root_hash),
+                "auditPath": [self.hashToStr(h) for h in audit_path]}
+
+    def append(self, txn):
+        return self.add(txn)
+
+    def getBySeqNo(self, seqNo):
+        seqNo = int(seqNo)
+        return self._transactionLog[seqNo - 1] if 0 < seqNo <= len(self._transactionLog) else None
+
+    def __getitem__(self, seqNo):
+        return self.getBySeqNo(seqNo)
+
+    def getAllTxn(self, frm=None, to=None):
+        lo = 1 if frm is None else max(1, int(frm))
+        hi = len(self._transactionLog) if to is None else min(int(to), len(self._transactionLog))
+        for seqNo in range(lo, hi + 1):
+            yield seqNo, self._transactionLog[seqNo - 1]
+
+    @property
+    def size(self):
+        return self.tree.tree_size
+
+    def __len__(self):
+        return self.size
+
+    @property
+    def root_hash(self):
+        return self.hashToStr(self.tree.root_hash)
+
+    def merkleInfo(self, seqNo):
+        seqNo = int(seqNo)
+        if seqNo <= 0:
+            raise ValueError("seqNo must be > 0, got %r" % (seqNo,))
+        return {"rootHash": self.hashToStr(self.tree.merkle_tree_hash(0, seqNo)),
+                "auditPath": [self.hashToStr(h) for h in self.tree.inclusion_proof(seqNo - 1, seqNo)]}
+
+    def reset(self):
+        """Destructive: the log and the hash store are emptied (the tree
+        object keeps its size and hashes until it is recovered, as in the
+        reference)."""
+        self._transactionLog = []
+        self.tree.hashStore.reset()
+
+    # ---- uncommitted transactions
+    @property
+    def uncommitted_size(self):
+        return self.size + len(self.uncommittedTxns)
+
+    def appendTxns(self, txns):
+        """Applied, not committed: only uncommittedTree and uncommittedRootHash move."""
+        txns = list(txns)
+        uncommittedSize = self.size + len(self.uncommittedTxns)
+        self.uncommittedTree = self.treeWithAppliedTxns(txns, self.uncommittedTree)
+        self.uncommittedRootHash = self.uncommittedTree.root_hash
+        self.uncommittedTxns.extend(txns)
+        if txns:
+            return (uncommittedSize + 1, uncommittedSize + len(txns)), txns
+        return (uncommittedSize, uncommittedSize), txns
+
+    def commitTxns(self, count):
+        """Commit the first `count` uncommitted transactions: one append_batch,
+        then every committed transaction is updated with its own rootHash and
+        auditPath (a transaction without `update`, such as bytes, is left as it
+        is).  Returns ((first seqNo, last seqNo), committed transactions)."""
+        committedSize = self.size
+        committedTxns = self.uncommittedTxns[:count]
+        if committedTxns:
+            logged = [copy(t) for t in committedTxns]  # as hashed: before the update
+            batch = self.tree.append_batch([self.serialize_for_tree(t) for t in committedTxns],
+                                           on_device=self.on_device, device=self.device)
+            for txn, (root, audit_path) in zip(committedTxns, batch):
+                if hasattr(txn, "update"):
+                    txn.update({"rootHash": self.hashToStr(root),
+                                "auditPath": [self.hashToStr(h) for h in audit_path]})
+            self._transactionLog.extend(logged)
+            self.seqNo += len(committedTxns)
+        self.uncommittedTxns = self.uncommittedTxns[count:]
+        if not self.uncommittedTxns:
+            self.uncommittedTree = None
+            self.uncommittedRootHash = None
+        if committedTxns:
+            return (committedSize + 1, committedSize + count), committedTxns
+        return (committedSize, committedSize), committedTxns
+
+    def discardTxns(self, count):
+        """Drop the last `count` uncommitted transactions."""
+        if count == 0:
+            return
+        self.uncommittedTxns = self.uncommittedTxns[:-count]
+        if not self.uncommittedTxns:
+            self.uncommittedTree = None
+            self.uncommittedRootHash = None
+        else:
+            self.uncommittedTree = self.treeWithAppliedTxns(self.uncommittedTxns)
+            self.uncommittedRootHash = self.uncommittedTree.root_hash
+
+    def treeWithAppliedTxns(self, txns, currentTree=None):
+        """A copy of the tree (the committed one unless given) with txns applied."""
+        currentTree = currentTree if currentTree is not None else self.tree
+        tempTree = copy(currentTree)
+        tempTree.extend([self.serialize_for_tree(t) for t in txns], on_device=self.on_device, device=self.device)
+        return tempTree
+
+    def reset_uncommitted(self):
+        self.uncommittedTxns = []
+        self.uncommittedRootHash = None
+        self.uncommittedTree = None
+
+    @staticmethod
+    def hashToStr(h):
+        return base58.b58encode(h).decode("utf-8")
+
+    @staticmethod
+    def strToHash(s):
+        return base58.b58decode(s)

@@ -15,6 +15,12 @@ which Ledger never uses; that state is not reproduced.)  With the device it is
 one edv_merkle_extend call per EDV_MERKLE_MAX_LEAVES leaves (gfx950 kernels
 edv_merkle_pass_kernel / edv_merkle_finish_kernel); `append`, the proofs and
 everything that reads the store stay on the host.
+
+`append_batch` (row f-6) is `extend` that also returns what each `append`
+returns (ledger/ledger.py:145-155: the audit path, and the root hash read after
+it), one edv_merkle_append_batch call per batch (kernel
+edv_merkle_append_kernel after the extend's): what `Ledger.commitTxns`
+(ledger.py) needs for a 3PC batch.
 """
 import hashlib
 from binascii import hexlify
@@ -29,6 +35,15 @@ from . import edv
 # leaves of 256 bytes; at 64 the host loop wins, 61 us against 131 us)
 MIN_DEVICE_LEAVES = 256
 
+# append_batch(on_device=None) takes the device from this many leaves on: the
+# smallest measured size at which the host-buffer call with roots and paths
+# beats the host loop on both trees (profiles/r08/merkle_append_bench.json,
+# "crossover": 234 us against 610 us at 256 leaves of 256 bytes onto an empty
+# tree, 354 us against 844 us onto 2^20 + 12,345 leaves; at 100, the next size
+# measured, the two are level within the rows' spread, 220 us against 218 us
+# and 334 us against 326 us; nothing between 100 and 256 was measured)
+MIN_DEVICE_APPEND_LEAVES = 256
+
 
 class ConsistencyVerificationFailed(Exception):
     pass
@@ -36,6 +51,51 @@ class ConsistencyVerificationFailed(Exception):
 
 def _popcount(x):
     return bin(x).count("1")
+
+
+def popcount_prefix(x):
+    """Sum of popcount(t) over 0 <= t < x: bit b is set in (x >> (b + 1)) 2^b
+    numbers below x, plus the part of x's last period past its first half."""
+    total = 0
+    for b in range(x.bit_length()):
+        half = 1 << b
+        total += ((x >> (b + 1)) << b) + max(0, (x & (2 * half - 1)) - half)
+    return total
+
+
+class AppendBatch:
+    """What the n `append` calls of one append_batch returned: `roots`, an
+    (n, 32) uint8 array (the root hash after leaf i), and the audit paths,
+    packed in `paths`, an (entries, 32) uint8 array: leaf i's path is the
+    popcount(old_size + i) rows from popcount_prefix(old_size + i) -
+    popcount_prefix(old_size) on, smallest subtree first.  Iterating yields
+    (root, audit_path) per leaf, as bytes and a list of bytes."""
+
+    def __init__(self, old_size, roots, paths):
+        self.old_size = old_size
+        self.roots = roots
+        self.paths = paths
+        self._base = popcount_prefix(old_size)
+
+    def __len__(self):
+        return len(self.roots)
+
+    def root(self, i):
+        return self.roots[i].tobytes()
+
+    def path(self, i):
+        if not 0 <= i < len(self.roots):
+            raise IndexError(i)
+        lo = popcount_prefix(self.old_size + i) - self._base
+        blob = self.paths[lo:lo + _popcount(self.old_size + i)].tobytes()
+        return [blob[k:k + 32] for k in range(0, len(blob), 32)]
+
+    def __iter__(self):
+        roots, blob, lo = self.roots.tobytes(), self.paths.tobytes(), 0
+        for i in range(len(self.roots)):
+            hi = lo + 32 * _popcount(self.old_size + i)
+            yield roots[32 * i:32 * i + 32], [blob[k:k + 32] for k in range(lo, hi, 32)]
+            lo = hi
 
 
 def node_position(height, block):
@@ -254,16 +314,77 @@ class CompactMerkleTree:
                 self.__hashStore.writeNodes(b"".join(h for _, _, h in nodes))
                 self._update(size, hashes)
 
-    def _extend_device(self, part, device):
+    def _device_call(self, part, device, per_leaf):
+        """One device call over `part`, tree and hash store updated from its
+        outputs; with per_leaf the appends' (roots, packed paths), else None."""
         off = np.zeros(len(part) + 1, dtype=np.uint64)
         off[1:] = np.cumsum([len(x) for x in part], dtype=np.uint64)
         blob = np.frombuffer(b"".join(part) + b"\0" * 8, dtype=np.uint8)
-        leaf_h, node_h, new_h, root = edv.merkle_extend(self.__tree_size, b"".join(self.__hashes), blob, off,
-                                                        device=device)
+        call = edv.merkle_append_batch if per_leaf else edv.merkle_extend
+        leaf_h, node_h, new_h, root, *rest = call(self.__tree_size, b"".join(self.__hashes), blob, off, device=device)
         self.__hashStore.writeLeafs(leaf_h)
         self.__hashStore.writeNodes(node_h)
         self._update(self.__tree_size + len(part), [bytes(r) for r in new_h])
         self.__root_hash = root
+        return tuple(rest) if per_leaf else None
+
+    def _extend_device(self, part, device):
+        self._device_call(part, device, False)
+
+    def append_batch(self, new_leaves, on_device=None, max_call=None, device=0):
+        """Append every leaf of new_leaves and return what each `append`
+        returns, as an AppendBatch: the root hash after every leaf and every
+        leaf's audit path.  Tree and hash store end exactly as after
+        len(new_leaves) calls of append.  on_device True / False forces the
+        path; None takes the device (one edv_merkle_append_batch call per
+        max_call leaves) from MIN_DEVICE_APPEND_LEAVES leaves on."""
+        new_leaves = list(new_leaves)
+        if on_device is None:
+            on_device = len(new_leaves) >= MIN_DEVICE_APPEND_LEAVES
+        step = edv.MERKLE_MAX_LEAVES if max_call is None else int(max_call)
+        if step < 1 or step > edv.MERKLE_MAX_LEAVES:
+            raise ValueError("max_call must be in [1, %d]" % edv.MERKLE_MAX_LEAVES)
+        if self.__tree_size + len(new_leaves) > edv.MERKLE_MAX_SIZE:
+            raise ValueError("tree size above 2^62")
+        old_size = self.__tree_size
+        roots, paths = [], []
+        for lo in range(0, len(new_leaves), step):
+            part = new_leaves[lo:lo + step]
+            r, p = self._append_batch_device(part, device) if on_device else self._append_batch_host(part)
+            roots.append(r)
+            paths.append(p)
+        if not roots:
+            roots, paths = [np.zeros((0, 32), np.uint8)], [np.zeros((0, 32), np.uint8)]
+        return AppendBatch(old_size, roots[0] if len(roots) == 1 else np.concatenate(roots),
+                           paths[0] if len(paths) == 1 else np.concatenate(paths))
+
+    def _append_batch_host(self, part):
+        """The appends one by one in hashlib: stack before, carry chain, fold after."""
+        hasher, store = self.__hasher, self.__hashStore
+        size, stack = self.__tree_size, list(self.__hashes)
+        roots, paths = [], []
+        for leaf in part:
+            paths.extend(reversed(stack))
+            h = hasher.hash_leaf(leaf)
+            store.writeLeaf(h)
+            size += 1
+            stack.append(h)
+            height, s = 1, size
+            while not s & 1:
+                right = stack.pop()
+                left = stack.pop()
+                stack.append(hasher.hash_children(left, right))
+                store.writeNode((size, height, stack[-1]))
+                height += 1
+                s >>= 1
+            roots.append(hasher.hash_fold(stack))
+        self._update(size, stack)
+        self.__root_hash = roots[-1] if roots else None
+        return (np.frombuffer(b"".join(roots), np.uint8).reshape(-1, 32),
+                np.frombuffer(b"".join(paths), np.uint8).reshape(-1, 32))
+
+    def _append_batch_device(self, part, device):
+        return self._device_call(part, device, True)
 
     def extended(self, new_leaves, on_device=None):
         """A new tree equal to this one extended with new_leaves (its own, empty, hash store)."""

@@ -13,6 +13,19 @@ For 65,536 leaves of 256 bytes, from old = 0 and from old = 2^20 + 12,345
 and (d) against (e) at n = 64 ... 16,384, whose smallest n with d < e is
 MIN_DEVICE_LEAVES (indy_plenum_amd/merkle.py).
 
+With --leg append: the batched append (row f-6) instead, written to
+profiles/r08/merkle_append_bench.json.  For 100, 256, 1,000, 10,000 and 65,536
+leaves of 256 bytes, from old = 0 and from old = 2^20 + 12,345:
+  a  edv_merkle_append_batch_dev      device-resident, all outputs
+  b  edv_merkle_append_batch          host buffers, roots only (with leaf and node hashes, as the tree asks)
+  c  edv_merkle_append_batch          host buffers, roots and audit paths
+  d  edv_merkle_extend_dev / edv_merkle_extend   the same leaves without the per-leaf outputs
+  e  CompactMerkleTree.append_batch(on_device=False)   the host hashlib loop
+with the fold hashes and path entries per leaf and the append kernel's lane
+efficiency (mean over the waves of mean / max trip count of the fold, from the
+sizes alone).  The smallest size from which (c) beats (e) on both trees is
+MIN_DEVICE_APPEND_LEAVES (indy_plenum_amd/merkle.py).
+
 Every figure is wall clock around calls that end in a device synchronise (the
 device forms with stream = NULL synchronise the library stream before they
 return), the median of 5 repetitions after a warm-up; a repetition repeats
@@ -72,15 +85,114 @@ def host_tree(old, fr, leaves):
     return t
 
 
+APPEND_SIZES = (100, 256, 1000, 10000, 65536)
+
+
+def lane_efficiency(old, n, lanes=64):
+    """The fold's trip counts (popcount(s) - 1 node hashes for s = old + i + 1) over the append kernel's
+    waves of `lanes` consecutive leaves: (mean over waves of mean / max trips, fold hashes per leaf)."""
+    trips = np.array([bin(old + i + 1).count("1") - 1 for i in range(n)], dtype=np.float64)
+    eff = []
+    for lo in range(0, n, lanes):
+        w = trips[lo:lo + lanes]
+        eff.append(w.mean() / w.max() if w.max() else 1.0)
+    return float(np.mean(eff)), float(trips.mean())
+
+
+def append_leg(args, rng):
+    """The batched append against the extend and the host loop (module docstring)."""
+    res = {"leaf_bytes": LEAF_BYTES, "window_s": args.window, "version": edv.version(), "rows": []}
+    blob = rng.integers(0, 256, N_BIG * LEAF_BYTES + 8, dtype=np.uint8)
+    off = np.arange(N_BIG + 1, dtype=np.uint64) * np.uint64(LEAF_BYTES)
+    leaves = [blob[i * LEAF_BYTES:(i + 1) * LEAF_BYTES].tobytes() for i in range(N_BIG)]
+    d_blob, d_off = dev(blob), dev(off)
+    for old in OLDS:
+        fr = frontier(rng, old)
+        frl = [fr[i:i + 32].tobytes() for i in range(0, len(fr), 32)]
+        d_old = dev(fr) if old else None
+        for n in APPEND_SIZES:
+            nodes = edv.merkle_node_span(old, n)
+            entries = edv.merkle_path_entries(old, n)
+            d_lh, d_nh = edv.DeviceBuffer(32 * n), edv.DeviceBuffer(32 * max(1, nodes))
+            d_new, d_root = edv.DeviceBuffer(32 * 64), edv.DeviceBuffer(32)
+            d_roots, d_paths = edv.DeviceBuffer(32 * n), edv.DeviceBuffer(32 * max(1, entries))
+            sub_blob, sub_off, sub_leaves = blob[:n * LEAF_BYTES + 8], off[:n + 1], leaves[:n]
+            oldp = d_old.ptr if d_old else None
+
+            def a():
+                edv.merkle_append_batch_device(old, oldp, d_blob.ptr, d_off.ptr, n, d_lh.ptr, d_nh.ptr, d_new.ptr,
+                                               d_root.ptr, d_roots.ptr, d_paths.ptr, device=args.device)
+
+            def b():
+                return edv.merkle_append_batch(old, fr, sub_blob, sub_off, want_audit_paths=False, device=args.device)
+
+            def c():
+                return edv.merkle_append_batch(old, fr, sub_blob, sub_off, device=args.device)
+
+            def d_dev():
+                edv.merkle_extend_device(old, oldp, d_blob.ptr, d_off.ptr, n, d_lh.ptr, d_nh.ptr, d_new.ptr,
+                                         d_root.ptr, device=args.device)
+
+            def d_host():
+                return edv.merkle_extend(old, fr, sub_blob, sub_off, device=args.device)
+
+            def e():
+                t = merkle.CompactMerkleTree(tree_size=old, hashes=frl)
+                return t, t.append_batch(sub_leaves, on_device=False)
+
+            # results first: (a) and (c) equal the host loop
+            t, batch = e()
+            a()
+            lh, nh, new, root, roots, paths = c()
+            assert root == t.root_hash == roots[-1].tobytes() and d_root.download().tobytes() == root
+            assert roots.tobytes() == batch.roots.tobytes() == d_roots.download().tobytes()
+            assert paths.tobytes() == batch.paths.tobytes() == d_paths.download(32 * entries).tobytes()
+            assert nh.tobytes() == bytes(t.hashStore._nodes) and lh.tobytes() == bytes(t.hashStore._leafs)
+            eff, folds = lane_efficiency(old, n)
+            row = {"old": old, "n": n, "path_entries_per_leaf": entries / n, "fold_hashes_per_leaf": folds,
+                   "lane_efficiency": eff,
+                   "a_append_batch_dev": timed(a, args.window),
+                   "b_append_batch_host_buffers_roots": timed(b, args.window),
+                   "c_append_batch_host_buffers_roots_paths": timed(c, args.window),
+                   "d_extend_dev": timed(d_dev, args.window),
+                   "d_extend_host_buffers": timed(d_host, args.window),
+                   "e_python_host_loop": timed(e, args.window)}
+            row["c_beats_e"] = (row["c_append_batch_host_buffers_roots_paths"]["median_us"]
+                                < row["e_python_host_loop"]["median_us"])
+            res["rows"].append(row)
+            print(json.dumps(row), flush=True)
+    # the crossover: the smallest size from which the host-buffer call with roots and paths wins on every tree
+    cross = None
+    for n in sorted(APPEND_SIZES, reverse=True):
+        if all(r["c_beats_e"] for r in res["rows"] if r["n"] == n):
+            cross = n
+        else:
+            break
+    res["crossover"] = {"min_device_append_leaves": cross,
+                        "rule": "smallest measured n from which c < e for every old, at n and every larger n"}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r07", "merkle_bench.json"))
+    ap.add_argument("--leg", choices=("extend", "append"), default="extend")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--window", type=float, default=0.2)
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "r07", "merkle_bench.json") if args.leg == "extend" else \
+            os.path.join(ROOT, "profiles", "r08", "merkle_append_bench.json")
     if edv.device_count() < 1:
         sys.exit("bench_merkle needs a gfx950 GPU")
     rng = np.random.default_rng(0x6962)
+    if args.leg == "append":
+        res = append_leg(args, rng)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+        print("wrote", args.out)
+        return
     res = {"leaves": N_BIG, "leaf_bytes": LEAF_BYTES, "window_s": args.window, "version": edv.version(),
            "big": [], "crossover": []}
 
