@@ -264,6 +264,80 @@ int edv_merkle_append_batch_dev(uint64_t old_size, const uint8_t *d_old_hashes,
 int edv_merkle_path_entries(uint64_t old_size, uint64_t n, uint64_t *entries);
 
 /*
+ * Batched proof verification (row f-7): what the reference's MerkleVerifier
+ * (ledger/merkle_verifier.py) checks one proof at a time for a client
+ * (plenum/client/client.py:846-873, verifyMerkleProof) and for a node in
+ * catch-up (plenum/common/ledger_manager.py:564-609), for n proofs in one
+ * call: RFC 6962 section 2.1.1 audit paths and 2.1.2 consistency proofs, one
+ * lane per proof.  Every uint64_t tree size is valid (a walk is at most 64
+ * levels).
+ *   proofs      packed 32-byte entries, lowest level first
+ *   proof_off   n + 1 non-decreasing offsets IN ENTRIES: proof i is entries
+ *               [proof_off[i], proof_off[i + 1]).  This is the layout
+ *               edv_merkle_append_batch writes: its audit_paths and roots, with
+ *               offsets from edv_merkle_path_entries(old_size, i, ..), feed the
+ *               device form unchanged (leaf i has index old_size + i in the
+ *               tree of old_size + i + 1 leaves)
+ *   leaves / leaf_off   the leaf bytes, laid out as msgs / msg_off everywhere
+ *               else and readable 8 bytes past the end; the lane hashes its
+ *               leaf itself.  Or
+ *   leaf_hashes n x 32 bytes.  Exactly one of leaves and leaf_hashes is given
+ *   roots       n x 32 bytes: the root hash each proof must arrive at
+ *   status      n bytes, one EDV_PROOF_* each (0 never means good)
+ *   computed    NULL, or n x 32 bytes: the root the walk calculated where it
+ *               ran to its end (OK, LONG, ROOT), zeros otherwise.  Consistency:
+ *               n x 64 bytes, the calculated old root, then the new one
+ *               (zeros where no walk is made: RANGE, SHORT, equal sizes,
+ *               old_size 0)
+ * Inclusion, in this order: RANGE, SHORT, LONG, ROOT.  Consistency: old > new
+ * is RANGE; equal sizes are OK if the roots are equal, else INCONSISTENT, and
+ * old_size 0 is OK (the proof is ignored in both); else SHORT, ROOT (the new
+ * root differs), INCONSISTENT (only the old one does); surplus entries after
+ * the walk are accepted.
+ * n = 0 is valid and writes nothing.  EDV_E_ARG with nothing launched or
+ * written: n above EDV_MERKLE_MAX_LEAVES; both leaves and leaf_hashes; with
+ * n > 0 neither of them, or NULL leaf_off (with leaves), leaf_index,
+ * tree_size / old_size / new_size, roots, proofs, proof_off or status; host
+ * offsets that decrease.
+ * Host form: fills status with EDV_PROOF_UNVERIFIED, stages in buffers of its
+ * own, synchronous.  The staging counts in edv_context_memory out[2]; edv_trim
+ * frees what a batch of keep_batch proofs of at most 64 entries would not
+ * need (all for 0), edv_release all of it.  A process that never calls the
+ * host forms allocates nothing for them.
+ */
+#define EDV_PROOF_UNVERIFIED 0   /* never written by a kernel: what the host form fills the buffer with first */
+#define EDV_PROOF_OK 1
+#define EDV_PROOF_RANGE 2        /* leaf_index >= tree_size (tree_size 0 included) / old_size > new_size */
+#define EDV_PROOF_SHORT 3        /* the walk needed an entry past the proof's end */
+#define EDV_PROOF_LONG 4         /* inclusion only: entries left over after the walk */
+#define EDV_PROOF_ROOT 5         /* the computed root (inclusion) / new root (consistency) differs */
+#define EDV_PROOF_INCONSISTENT 6 /* consistency only: the new root matches and the old one does not */
+int edv_merkle_verify_inclusion(const uint8_t *leaves, const uint64_t *leaf_off, const uint8_t *leaf_hashes,
+                                const uint64_t *leaf_index, const uint64_t *tree_size, const uint8_t *roots,
+                                const uint8_t *proofs, const uint64_t *proof_off, uint64_t n,
+                                uint8_t *status, uint8_t *computed, int device);
+int edv_merkle_verify_consistency(const uint64_t *old_size, const uint64_t *new_size, const uint8_t *old_roots,
+                                  const uint8_t *new_roots, const uint8_t *proofs, const uint64_t *proof_off,
+                                  uint64_t n, uint8_t *status, uint8_t *computed, int device);
+/* Device-resident forms, async on `stream` (NULL = library stream,
+ * synchronised before returning); offsets are absolute minus leaf_base /
+ * proof_base, as in edv_verify_batch_dev.  They use no context memory, so
+ * calls on any streams are ordered by their streams alone.  Also EDV_E_ARG,
+ * with nothing launched: a 64-bit array (offsets, indices, sizes) not 8-byte
+ * aligned, a hash buffer (d_leaf_hashes, d_roots, d_old_roots, d_new_roots,
+ * d_proofs, d_computed) not 16-byte aligned; d_status and d_leaves may have
+ * any alignment.  The offsets live in device memory and are not checked. */
+int edv_merkle_verify_inclusion_dev(const uint8_t *d_leaves, const uint64_t *d_leaf_off, uint64_t leaf_base,
+                                    const uint8_t *d_leaf_hashes, const uint64_t *d_leaf_index,
+                                    const uint64_t *d_tree_size, const uint8_t *d_roots,
+                                    const uint8_t *d_proofs, const uint64_t *d_proof_off, uint64_t proof_base, uint64_t n,
+                                    uint8_t *d_status, uint8_t *d_computed, int device, void *stream);
+int edv_merkle_verify_consistency_dev(const uint64_t *d_old_size, const uint64_t *d_new_size,
+                                      const uint8_t *d_old_roots, const uint8_t *d_new_roots,
+                                      const uint8_t *d_proofs, const uint64_t *d_proof_off, uint64_t proof_base, uint64_t n,
+                                      uint8_t *d_status, uint8_t *d_computed, int device, void *stream);
+
+/*
  * Pipelined submission of device-resident batches (a continuous stream of
  * client batches, e.g. one per Node prod): enqueues the batch and returns
  * without waiting.  Consecutive submissions alternate between two internal

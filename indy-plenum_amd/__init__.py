@@ -11,11 +11,14 @@ client-inbox batch to the HIP kernels through the C-ABI in include/edv.h.
 """
 __version__ = "0.1.0"
 
-__all__ = ["Ledger"]
+__all__ = ["Ledger", "MerkleVerifier", "STH", "verify_merkle_proofs"]
 
 
-def __getattr__(name):  # the ledger (row f-6), imported on first use
-    if name == "Ledger":
-        from .ledger import Ledger
-        return Ledger
+def __getattr__(name):  # the ledger (rows f-6, f-7), imported on first use
+    if name in ("Ledger", "verify_merkle_proofs"):
+        from . import ledger
+        return getattr(ledger, name)
+    if name in ("MerkleVerifier", "STH"):
+        from . import merkle
+        return getattr(merkle, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -723,4 +723,96 @@ int hc_merkle_append_batch(uint64_t old_size, const uint8_t* old_hashes, const u
   if (audit_paths && entries) memcpy(audit_paths, pathsw.data(), 32 * entries);
   return 0;
 }
+// ---- proof verification (edv_merkle.h, row f-7)
+// The host C-ABI forms' signatures minus `device`: the kernels' lanes one after
+// another.  Every input goes into a heap block of exactly its documented size
+// (the leaves: 8 bytes more, their alignment relative to their offsets kept),
+// so a lane reading past a proof's last entry is ASan's to see.
+static bool hc_offsets_ok(const uint64_t* off, uint64_t n) {
+  for (uint64_t i = 0; i < n; i++)
+    if (off[i + 1] < off[i]) return false;
+  return true;
+}
+int hc_merkle_verify_inclusion(const uint8_t* leaves, const uint64_t* leaf_off, const uint8_t* leaf_hashes,
+                               const uint64_t* leaf_index, const uint64_t* tree_size, const uint8_t* roots,
+                               const uint8_t* proofs, const uint64_t* proof_off, uint64_t n, uint8_t* status,
+                               uint8_t* computed) {
+  if (n > (uint64_t(1) << 22) || (leaves && leaf_hashes)) return -1;
+  if (n == 0) return 0;
+  if ((!leaves && !leaf_hashes) || (leaves && !leaf_off) || !leaf_index || !tree_size || !roots || !proofs || !proof_off ||
+      !status)
+    return -1;
+  if ((leaves && !hc_offsets_ok(leaf_off, n)) || !hc_offsets_ok(proof_off, n)) return -1;
+  memset(status, kProofUnverified, n);
+  const uint64_t lbase = leaves ? leaf_off[0] : 0, lbytes = leaves ? leaf_off[n] - leaf_off[0] : 0;
+  const uint64_t pbase = proof_off[0], entries = proof_off[n] - proof_off[0];
+  std::vector<uint32_t> lbuf(leaves ? (lbytes + (lbase & 3) + 8 + 3) / 4 : 0), lhw(leaves ? 0 : 8 * n), rootw(8 * n),
+      proofw(8 * entries), compw(computed ? 8 * n : 0);
+  std::vector<uint64_t> loff(leaves ? n + 1 : 0), idx(leaf_index, leaf_index + n), size(tree_size, tree_size + n),
+      poff(proof_off, proof_off + n + 1);
+  uint8_t* lv = reinterpret_cast<uint8_t*>(lbuf.data()) + (lbase & 3);
+  if (leaves) {
+    memcpy(loff.data(), leaf_off, 8 * (n + 1));
+    if (lbytes) memcpy(lv, leaves + lbase, lbytes);
+  } else {
+    memcpy(lhw.data(), leaf_hashes, 32 * n);
+  }
+  memcpy(rootw.data(), roots, 32 * n);
+  if (entries) memcpy(proofw.data(), proofs + 32 * pbase, 32 * entries);
+  std::vector<uint8_t> st(n);
+  MerkleVerifyInclusion a;
+  a.n = n;
+  a.leaves = leaves ? lv : nullptr;
+  a.leaf_off = leaves ? loff.data() : nullptr;
+  a.leaf_base = lbase;
+  a.leaf_hashes = leaves ? nullptr : lhw.data();
+  a.leaf_index = idx.data();
+  a.tree_size = size.data();
+  a.roots = rootw.data();
+  a.proofs = proofw.data();
+  a.proof_off = poff.data();
+  a.proof_base = pbase;
+  a.status = st.data();
+  a.computed = computed ? compw.data() : nullptr;
+  for (uint64_t i = 0; i < n; i++) {
+    if (leaves)
+      merkle_verify_inclusion_lane<true>(a, i);
+    else
+      merkle_verify_inclusion_lane<false>(a, i);
+  }
+  memcpy(status, st.data(), n);
+  if (computed) memcpy(computed, compw.data(), 32 * n);
+  return 0;
+}
+int hc_merkle_verify_consistency(const uint64_t* old_size, const uint64_t* new_size, const uint8_t* old_roots,
+                                 const uint8_t* new_roots, const uint8_t* proofs, const uint64_t* proof_off, uint64_t n,
+                                 uint8_t* status, uint8_t* computed) {
+  if (n > (uint64_t(1) << 22)) return -1;
+  if (n == 0) return 0;
+  if (!old_size || !new_size || !old_roots || !new_roots || !proofs || !proof_off || !status) return -1;
+  if (!hc_offsets_ok(proof_off, n)) return -1;
+  memset(status, kProofUnverified, n);
+  const uint64_t pbase = proof_off[0], entries = proof_off[n] - proof_off[0];
+  std::vector<uint32_t> oldw(8 * n), neww(8 * n), proofw(8 * entries), compw(computed ? 16 * n : 0);
+  std::vector<uint64_t> os(old_size, old_size + n), ns(new_size, new_size + n), poff(proof_off, proof_off + n + 1);
+  memcpy(oldw.data(), old_roots, 32 * n);
+  memcpy(neww.data(), new_roots, 32 * n);
+  if (entries) memcpy(proofw.data(), proofs + 32 * pbase, 32 * entries);
+  std::vector<uint8_t> st(n);
+  MerkleVerifyConsistency a;
+  a.n = n;
+  a.old_size = os.data();
+  a.new_size = ns.data();
+  a.old_roots = oldw.data();
+  a.new_roots = neww.data();
+  a.proofs = proofw.data();
+  a.proof_off = poff.data();
+  a.proof_base = pbase;
+  a.status = st.data();
+  a.computed = computed ? compw.data() : nullptr;
+  for (uint64_t i = 0; i < n; i++) merkle_verify_consistency_lane(a, i);
+  memcpy(status, st.data(), n);
+  if (computed) memcpy(computed, compw.data(), 64 * n);
+  return 0;
+}
 }

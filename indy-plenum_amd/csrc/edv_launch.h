@@ -47,5 +47,12 @@ hipError_t launch_merkle_finish_kernel(hipStream_t s, uint64_t old_size, uint64_
 // on the same stream; no launch for n = 0 or with neither output wanted
 struct MerkleAppend;
 hipError_t launch_merkle_append_kernel(hipStream_t s, const MerkleAppend& a);
+// proof verification (MerkleVerifyInclusion / MerkleVerifyConsistency:
+// edv_merkle.h), one lane per proof; a.leaves non-null: the lanes hash their
+// leaves, else they read a.leaf_hashes; no launch for n = 0
+struct MerkleVerifyInclusion;
+struct MerkleVerifyConsistency;
+hipError_t launch_merkle_verify_inclusion_kernel(hipStream_t s, const MerkleVerifyInclusion& a);
+hipError_t launch_merkle_verify_consistency_kernel(hipStream_t s, const MerkleVerifyConsistency& a);
 
 }  // namespace edv

@@ -1,6 +1,8 @@
 // edv_merkle.h -- extending a compact RFC 6962 Merkle tree by a batch of leaves
 // (SURVEY.md section 8f row f-5), and what each of the appends returns: the
-// root after it and its audit path (row f-6, at the end of this file).
+// root after it and its audit path (row f-6), and the checking of such proofs:
+// audit paths and consistency proofs, a batch at a time (row f-7, at the end of
+// this file; ledger/merkle_verifier.py MerkleVerifier).
 //
 // Replaces, per batch of transactions:
 //   ledger/ledger.py:145-148              Ledger._addToTree (one append per txn)
@@ -386,6 +388,199 @@ EDV_HD void merkle_append_leaf(const MerkleAppend& a, uint64_t i) {
       merkle_copy_hash(out, merkle_entry(a, s - 1, b));
       out += 8;
     }
+  }
+}
+
+// ---- proof verification (row f-7: what MerkleVerifier checks, one lane per proof)
+// Written from RFC 6962 sections 2.1.1 (audit paths) and 2.1.2 (consistency
+// proofs).  A proof is `count` 32-byte entries, lowest level first; a walk
+// never reads an entry at or past `count`.  One status byte per proof; 0 is
+// never written by a walk, so a buffer nothing wrote rejects.
+constexpr uint8_t kProofUnverified = 0;    // EDV_PROOF_* of include/edv.h
+constexpr uint8_t kProofOk = 1;
+constexpr uint8_t kProofRange = 2;         // leaf_index >= tree_size / old_size > new_size
+constexpr uint8_t kProofShort = 3;         // the walk needed an entry past the proof's end
+constexpr uint8_t kProofLong = 4;          // inclusion: entries left over after the walk
+constexpr uint8_t kProofRoot = 5;          // the computed (new) root differs
+constexpr uint8_t kProofInconsistent = 6;  // consistency: new root matches, old root does not
+// did the walk run to its end (`computed` holds what it calculated)?
+EDV_HD bool merkle_proof_walked(uint8_t st) { return st == kProofOk || st >= kProofLong; }
+EDV_HD bool merkle_hash_equal(const uint32_t a[8], const uint32_t b[8]) {
+  uint32_t d = 0;
+#pragma unroll
+  for (int w = 0; w < 8; w++) d |= a[w] ^ b[w];
+  return d == 0;
+}
+
+// Audit path of leaf `leaf_index` in the tree of `tree_size` leaves (any
+// uint64_t size, at most 64 levels): node = leaf_index, last = tree_size - 1,
+// upwards while last > 0.  An odd node has a left sibling, an even node below
+// `last` a right one, an even node that is the last of its level none (no
+// entry, no hash).  Both kinds of sibling go through one node hash with the
+// operands selected, so lanes on different sides of their parents stay
+// together.  acc: the leaf hash in, the calculated root out (when the walk
+// ran to its end).  Precedence: RANGE, SHORT, LONG, ROOT.
+EDV_HD uint8_t merkle_verify_inclusion_one(uint32_t acc[8], uint64_t leaf_index, uint64_t tree_size,
+                                           const uint32_t* path, uint64_t count, const uint32_t root[8]) {
+  if (leaf_index >= tree_size) return kProofRange;
+  uint64_t node = leaf_index, last = tree_size - 1, used = 0;
+#pragma unroll 1
+  while (last > 0) {
+    const bool odd = (node & 1) != 0;
+    if (odd || node < last) {
+      if (used == count) return kProofShort;
+      uint32_t e[8], l[8], r[8];
+      merkle_load_hash(e, path + 8 * used);
+      used++;
+#pragma unroll
+      for (int w = 0; w < 8; w++) {
+        l[w] = odd ? e[w] : acc[w];
+        r[w] = odd ? acc[w] : e[w];
+      }
+      merkle_node_hash(acc, l, r);
+    }
+    node >>= 1;
+    last >>= 1;
+  }
+  if (used != count) return kProofLong;
+  return merkle_hash_equal(acc, root) ? kProofOk : kProofRoot;
+}
+
+// Consistency of the trees of old_size and new_size leaves.  old > new: RANGE;
+// equal sizes: the roots decide, the proof is ignored; old = 0: OK, anything is
+// consistent with the empty tree.  Otherwise node = old - 1, last = new - 1,
+// both shifted right while node is odd (that part is in both trees); the seed
+// of both accumulators is the first entry, or old_root when node is 0 (old is
+// a power of two).  Then upwards while last > 0: an odd node's left sibling
+// goes into both accumulators, an even node's right sibling (node < last) into
+// the new one only, an even last node has none.  Once node is 0 it stays even
+// and below last, so the same loop is the rest of the path up to the new
+// root.  Entries after the walk are accepted.  walked: false where no walk was
+// made (then oldr / newr hold nothing).  ROOT before INCONSISTENT.
+EDV_HD uint8_t merkle_verify_consistency_one(uint32_t oldr[8], uint32_t newr[8], bool* walked, uint64_t old_size,
+                                             uint64_t new_size, const uint32_t old_root[8], const uint32_t new_root[8],
+                                             const uint32_t* proof, uint64_t count) {
+  *walked = false;
+  if (old_size > new_size) return kProofRange;
+  if (old_size == new_size) return merkle_hash_equal(old_root, new_root) ? kProofOk : kProofInconsistent;
+  if (old_size == 0) return kProofOk;
+  uint64_t node = old_size - 1, last = new_size - 1, used = 0;
+  while (node & 1) {
+    node >>= 1;
+    last >>= 1;
+  }
+  if (node != 0) {
+    if (count == 0) return kProofShort;
+    merkle_load_hash(newr, proof);
+    used = 1;
+  } else {
+#pragma unroll
+    for (int w = 0; w < 8; w++) newr[w] = old_root[w];
+  }
+#pragma unroll
+  for (int w = 0; w < 8; w++) oldr[w] = newr[w];
+#pragma unroll 1
+  while (last > 0) {
+    const bool odd = (node & 1) != 0;
+    if (odd || node < last) {
+      if (used == count) return kProofShort;
+      uint32_t e[8], l[8], r[8];
+      merkle_load_hash(e, proof + 8 * used);
+      used++;
+      if (odd) {
+#pragma unroll
+        for (int w = 0; w < 8; w++) r[w] = oldr[w];
+        merkle_node_hash(oldr, e, r);
+      }
+#pragma unroll
+      for (int w = 0; w < 8; w++) {
+        l[w] = odd ? e[w] : newr[w];
+        r[w] = odd ? newr[w] : e[w];
+      }
+      merkle_node_hash(newr, l, r);
+    }
+    node >>= 1;
+    last >>= 1;
+  }
+  *walked = true;
+  if (!merkle_hash_equal(newr, new_root)) return kProofRoot;
+  return merkle_hash_equal(oldr, old_root) ? kProofOk : kProofInconsistent;
+}
+
+// One batch of inclusion proofs.  Proof i is entries [proof_off[i],
+// proof_off[i + 1]) - proof_base of `proofs` (the layout the batched append
+// writes); its leaf is bytes [leaf_off[i], leaf_off[i + 1]) - leaf_base of
+// `leaves` (kLeaves), or hash i of leaf_hashes.
+struct MerkleVerifyInclusion {
+  uint64_t n;
+  const uint8_t* leaves;        // kLeaves: readable 8 bytes past the last leaf byte
+  const uint64_t* leaf_off;
+  uint64_t leaf_base;
+  const uint32_t* leaf_hashes;  // !kLeaves
+  const uint64_t* leaf_index;
+  const uint64_t* tree_size;
+  const uint32_t* roots;
+  const uint32_t* proofs;
+  const uint64_t* proof_off;
+  uint64_t proof_base;
+  uint8_t* status;
+  uint32_t* computed;           // 8 words per proof, or null
+};
+// Lane i < a.n.  A lane out of range hashes no leaf.
+template <bool kLeaves>
+EDV_HD void merkle_verify_inclusion_lane(const MerkleVerifyInclusion& a, uint64_t i) {
+  const uint64_t idx = a.leaf_index[i], size = a.tree_size[i];
+  const uint64_t p0 = a.proof_off[i], p1 = a.proof_off[i + 1];
+  uint32_t acc[8], root[8];
+  uint8_t st = kProofRange;
+  if (idx < size) {
+    if (kLeaves) {
+      const uint64_t o0 = a.leaf_off[i] - a.leaf_base, o1 = a.leaf_off[i + 1] - a.leaf_base;
+      merkle_leaf_hash(acc, a.leaves + o0, o1 - o0);
+    } else {
+      merkle_load_hash(acc, a.leaf_hashes + 8 * i);
+    }
+    merkle_load_hash(root, a.roots + 8 * i);
+    st = merkle_verify_inclusion_one(acc, idx, size, a.proofs + 8 * (p0 - a.proof_base), p1 - p0, root);
+  }
+  a.status[i] = st;
+  if (a.computed) {
+    if (!merkle_proof_walked(st)) {
+#pragma unroll
+      for (int w = 0; w < 8; w++) acc[w] = 0;
+    }
+    merkle_store_hash(a.computed + 8 * i, acc);
+  }
+}
+
+struct MerkleVerifyConsistency {
+  uint64_t n;
+  const uint64_t* old_size;
+  const uint64_t* new_size;
+  const uint32_t* old_roots;
+  const uint32_t* new_roots;
+  const uint32_t* proofs;
+  const uint64_t* proof_off;
+  uint64_t proof_base;
+  uint8_t* status;
+  uint32_t* computed;  // 16 words per proof (old, then new), or null
+};
+EDV_HD void merkle_verify_consistency_lane(const MerkleVerifyConsistency& a, uint64_t i) {
+  const uint64_t p0 = a.proof_off[i], p1 = a.proof_off[i + 1];
+  uint32_t ro[8], rn[8], oldr[8], newr[8];
+  merkle_load_hash(ro, a.old_roots + 8 * i);
+  merkle_load_hash(rn, a.new_roots + 8 * i);
+  bool walked;
+  const uint8_t st = merkle_verify_consistency_one(oldr, newr, &walked, a.old_size[i], a.new_size[i], ro, rn,
+                                                   a.proofs + 8 * (p0 - a.proof_base), p1 - p0);
+  a.status[i] = st;
+  if (a.computed) {
+    if (!walked) {
+#pragma unroll
+      for (int w = 0; w < 8; w++) oldr[w] = newr[w] = 0;
+    }
+    merkle_store_hash(a.computed + 16 * i, oldr);
+    merkle_store_hash(a.computed + 16 * i + 8, newr);
   }
 }
 

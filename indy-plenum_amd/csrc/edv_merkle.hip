@@ -6,7 +6,8 @@
 // used in turn, one __syncthreads() per level.  Workgroups never talk to each
 // other: a pass reads what the pass before wrote, and passes are separate
 // launches on one stream.  The batched append (row f-6) adds one kernel after
-// them: one lane per new leaf, the root after it and its audit path.
+// them: one lane per new leaf, the root after it and its audit path.  Proof
+// verification (row f-7) is two kernels of the same shape: one lane per proof.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -58,6 +59,26 @@ __global__ __launch_bounds__(kMerkleAppendLanes) void edv_merkle_append_kernel(M
   if (i < a.n) merkle_append_leaf(a, i);
 }
 
+// Row f-7: one lane walks one proof (merkle_verify_inclusion_lane /
+// merkle_verify_consistency_lane): a serial chain of two compressions per
+// entry, so the batch is the parallelism.  As the append kernel: no LDS, no
+// lane talks to another, 64-lane workgroups so that a batch of a few thousand
+// proofs already spreads over the CUs; lanes of a wave differ in trip count
+// (path length, leaf length) and rejoin at the status store.  With leaf bytes
+// the lane hashes its own leaf first, in the same launch: a separate leaf-hash
+// launch would write and re-read 32 bytes per proof and add a kernel boundary
+// to save nothing, the leaf's blocks being one more serial stretch of the
+// lane's chain either way.
+template <bool kLeaves>
+__global__ __launch_bounds__(kMerkleAppendLanes) void edv_merkle_verify_inclusion_kernel(MerkleVerifyInclusion a) {
+  const uint64_t i = uint64_t(blockIdx.x) * kMerkleAppendLanes + threadIdx.x;
+  if (i < a.n) merkle_verify_inclusion_lane<kLeaves>(a, i);
+}
+__global__ __launch_bounds__(kMerkleAppendLanes) void edv_merkle_verify_consistency_kernel(MerkleVerifyConsistency a) {
+  const uint64_t i = uint64_t(blockIdx.x) * kMerkleAppendLanes + threadIdx.x;
+  if (i < a.n) merkle_verify_consistency_lane(a, i);
+}
+
 }  // namespace
 
 namespace edv {
@@ -84,6 +105,23 @@ hipError_t launch_merkle_append_kernel(hipStream_t s, const MerkleAppend& a) {
   if (a.n == 0 || (!a.roots && !a.paths)) return hipSuccess;
   const uint64_t blocks = (a.n + kMerkleAppendLanes - 1) / kMerkleAppendLanes;
   edv_merkle_append_kernel<<<dim3(unsigned(blocks)), dim3(kMerkleAppendLanes), 0, s>>>(a);
+  return hipGetLastError();
+}
+
+hipError_t launch_merkle_verify_inclusion_kernel(hipStream_t s, const MerkleVerifyInclusion& a) {
+  if (a.n == 0) return hipSuccess;
+  const uint64_t blocks = (a.n + kMerkleAppendLanes - 1) / kMerkleAppendLanes;
+  if (a.leaves)
+    edv_merkle_verify_inclusion_kernel<true><<<dim3(unsigned(blocks)), dim3(kMerkleAppendLanes), 0, s>>>(a);
+  else
+    edv_merkle_verify_inclusion_kernel<false><<<dim3(unsigned(blocks)), dim3(kMerkleAppendLanes), 0, s>>>(a);
+  return hipGetLastError();
+}
+
+hipError_t launch_merkle_verify_consistency_kernel(hipStream_t s, const MerkleVerifyConsistency& a) {
+  if (a.n == 0) return hipSuccess;
+  const uint64_t blocks = (a.n + kMerkleAppendLanes - 1) / kMerkleAppendLanes;
+  edv_merkle_verify_consistency_kernel<<<dim3(unsigned(blocks)), dim3(kMerkleAppendLanes), 0, s>>>(a);
   return hipGetLastError();
 }
 

@@ -245,9 +245,16 @@ struct DevCtx {
   // the host form's staging of the per-leaf roots and the packed audit paths
   DevBuf mk_fleafh, mk_fnodeh, mk_aroots, mk_paths;
   hipEvent_t mk_done = nullptr;
+  // proof verification (edv_merkle_verify_inclusion / _consistency): the host
+  // forms' staging, theirs alone while they hold mu (the device forms use no
+  // context memory).  mv_leaves: leaf bytes or leaf hashes; mv_words: every
+  // 64-bit input array, one after another; mv_roots: the given roots;
+  // mv_proofs: the packed entries; mv_out: computed roots, then the statuses.
+  DevBuf mv_leaves, mv_words, mv_roots, mv_proofs, mv_out;
   uint64_t mk_bytes() const {
     return mk_roots.cap + mk_leaves.cap + mk_off.cap + mk_hashes.cap + mk_leafh.cap + mk_nodeh.cap +
-           mk_fleafh.cap + mk_fnodeh.cap + mk_aroots.cap + mk_paths.cap;
+           mk_fleafh.cap + mk_fnodeh.cap + mk_aroots.cap + mk_paths.cap + mv_leaves.cap + mv_words.cap +
+           mv_roots.cap + mv_proofs.cap + mv_out.cap;
   }
 #ifdef EDV_MEASUREMENT_API
   int64_t inject_fail = -1;        // edv_test_fail_async (libedv_measure.so only)
@@ -1396,6 +1403,110 @@ int run_merkle_host(DevCtx& c, uint64_t old_size, const uint8_t* old_hashes, con
   return 0;
 }
 
+// ---- proof verification (edv_merkle.h, row f-7).  The host forms: inputs
+// staged in the context's mv_* buffers, one launch on the library stream, the
+// statuses (and the computed roots, if asked for) copied back, synchronous.
+// The 64-bit arrays go into mv_words one after another (each starts on a
+// multiple of 8 bytes); the windows [off[0], off[n]) of the leaf bytes and of
+// the proof entries are what is copied, and off[0] is the kernel's base.
+// Caller holds c.mu and has checked the arguments.
+struct WordStage {
+  uint64_t* base;
+  uint64_t used = 0;
+  hipStream_t s;
+  const uint64_t* put(const uint64_t* src, uint64_t count, hipError_t* e) {
+    uint64_t* d = base + used;
+    used += count;
+    if (*e == hipSuccess) *e = hipMemcpyAsync(d, src, 8 * count, hipMemcpyHostToDevice, s);
+    return d;
+  }
+};
+int stage_proofs(DevCtx& c, const uint8_t* proofs, const uint64_t* proof_off, uint64_t n, const uint32_t** d_proofs) {
+  const uint64_t bytes = 32 * (proof_off[n] - proof_off[0]);
+  if (c.mv_proofs.ensure(bytes ? bytes : 32)) return EDV_E_OOM;
+  if (bytes)
+    HIPOK(hipMemcpyAsync(c.mv_proofs.p, proofs + 32 * proof_off[0], bytes, hipMemcpyHostToDevice, c.stream),
+          "h2d proofs");
+  *d_proofs = static_cast<const uint32_t*>(c.mv_proofs.p);
+  return 0;
+}
+// launch(d_status, d_computed) runs the kernel; cbytes: computed bytes per proof
+template <class Launch>
+int run_proofs_out(DevCtx& c, uint64_t n, uint64_t cbytes, uint8_t* status, uint8_t* computed, Launch launch) {
+  uint8_t* d_comp = computed ? static_cast<uint8_t*>(c.mv_out.p) : nullptr;
+  uint8_t* d_status = static_cast<uint8_t*>(c.mv_out.p) + (computed ? cbytes * n : 0);
+  HIPOK(launch(d_status, reinterpret_cast<uint32_t*>(d_comp)), "merkle verify launch");
+  HIPOK(hipMemcpyAsync(status, d_status, n, hipMemcpyDeviceToHost, c.stream), "d2h proof status");
+  if (computed) HIPOK(hipMemcpyAsync(computed, d_comp, cbytes * n, hipMemcpyDeviceToHost, c.stream), "d2h computed roots");
+  HIPOK(hipStreamSynchronize(c.stream), "stream sync");
+  return 0;
+}
+
+int run_verify_inclusion_host(DevCtx& c, const uint8_t* leaves, const uint64_t* leaf_off, const uint8_t* leaf_hashes,
+                              const uint64_t* leaf_index, const uint64_t* tree_size, const uint8_t* roots,
+                              const uint8_t* proofs, const uint64_t* proof_off, uint64_t n, uint8_t* status,
+                              uint8_t* computed) {
+  const hipStream_t s = c.stream;
+  const uint64_t lbytes = leaves ? leaf_off[n] - leaf_off[0] : 32 * n;
+  if (c.mv_leaves.ensure(lbytes + kReadSlack) || c.mv_words.ensure(8 * (4 * n + 2)) || c.mv_roots.ensure(32 * n) ||
+      c.mv_out.ensure((computed ? 32 * n : 0) + n))
+    return EDV_E_OOM;
+  MerkleVerifyInclusion a;
+  int err;
+  if ((err = stage_proofs(c, proofs, proof_off, n, &a.proofs))) return err;
+  if (lbytes)
+    HIPOK(hipMemcpyAsync(c.mv_leaves.p, leaves ? leaves + leaf_off[0] : leaf_hashes, lbytes, hipMemcpyHostToDevice, s),
+          "h2d leaves");
+  HIPOK(hipMemcpyAsync(c.mv_roots.p, roots, 32 * n, hipMemcpyHostToDevice, s), "h2d roots");
+  WordStage w{static_cast<uint64_t*>(c.mv_words.p), 0, s};
+  hipError_t e = hipSuccess;
+  a.n = n;
+  a.leaves = leaves ? static_cast<const uint8_t*>(c.mv_leaves.p) : nullptr;
+  a.leaf_off = leaves ? w.put(leaf_off, n + 1, &e) : nullptr;
+  a.leaf_base = leaves ? leaf_off[0] : 0;
+  a.leaf_hashes = leaves ? nullptr : static_cast<const uint32_t*>(c.mv_leaves.p);
+  a.leaf_index = w.put(leaf_index, n, &e);
+  a.tree_size = w.put(tree_size, n, &e);
+  a.proof_off = w.put(proof_off, n + 1, &e);
+  a.proof_base = proof_off[0];
+  a.roots = static_cast<const uint32_t*>(c.mv_roots.p);
+  HIPOK(e, "h2d proof words");
+  return run_proofs_out(c, n, 32, status, computed, [&](uint8_t* d_status, uint32_t* d_comp) {
+    a.status = d_status;
+    a.computed = d_comp;
+    return launch_merkle_verify_inclusion_kernel(s, a);
+  });
+}
+
+int run_verify_consistency_host(DevCtx& c, const uint64_t* old_size, const uint64_t* new_size, const uint8_t* old_roots,
+                                const uint8_t* new_roots, const uint8_t* proofs, const uint64_t* proof_off, uint64_t n,
+                                uint8_t* status, uint8_t* computed) {
+  const hipStream_t s = c.stream;
+  if (c.mv_words.ensure(8 * (4 * n + 2)) || c.mv_roots.ensure(64 * n) || c.mv_out.ensure((computed ? 64 * n : 0) + n))
+    return EDV_E_OOM;
+  MerkleVerifyConsistency a;
+  int err;
+  if ((err = stage_proofs(c, proofs, proof_off, n, &a.proofs))) return err;
+  uint8_t* d_roots = static_cast<uint8_t*>(c.mv_roots.p);
+  HIPOK(hipMemcpyAsync(d_roots, old_roots, 32 * n, hipMemcpyHostToDevice, s), "h2d old roots");
+  HIPOK(hipMemcpyAsync(d_roots + 32 * n, new_roots, 32 * n, hipMemcpyHostToDevice, s), "h2d new roots");
+  WordStage w{static_cast<uint64_t*>(c.mv_words.p), 0, s};
+  hipError_t e = hipSuccess;
+  a.n = n;
+  a.old_size = w.put(old_size, n, &e);
+  a.new_size = w.put(new_size, n, &e);
+  a.proof_off = w.put(proof_off, n + 1, &e);
+  a.proof_base = proof_off[0];
+  a.old_roots = reinterpret_cast<const uint32_t*>(d_roots);
+  a.new_roots = reinterpret_cast<const uint32_t*>(d_roots + 32 * n);
+  HIPOK(e, "h2d proof words");
+  return run_proofs_out(c, n, 64, status, computed, [&](uint8_t* d_status, uint32_t* d_comp) {
+    a.status = d_status;
+    a.computed = d_comp;
+    return launch_merkle_verify_consistency_kernel(s, a);
+  });
+}
+
 // Asynchronous host path.  Wait for a slot's batch and hand over its verdicts.
 void async_fail(DevCtx& c, DevCtx::AsyncSlot& s) {
   c.ledger.fail(s.ticket);
@@ -1753,6 +1864,12 @@ void trim_buffers(DevCtx& c, uint64_t keep) {
   dev(c.mk_fnodeh, 32 * k);
   dev(c.mk_aroots, 32 * k);
   dev(c.mk_paths, 32 * kMerkleMaxHashes * k);  // a path is at most kMerkleMaxHashes entries
+  // proof verification: k proofs of at most 64 entries, leaves of kTrimMsgBytes
+  dev(c.mv_leaves, k ? t.msgs : 0);
+  dev(c.mv_words, k ? 8 * (4 * k + 2) : 0);
+  dev(c.mv_roots, 64 * k);
+  dev(c.mv_proofs, 32 * 64 * k);
+  dev(c.mv_out, 80 * k);  // 64 computed bytes (consistency) and the status, rounded up to 16
   for (auto& a : c.as) {
     set(a.cb);
     dev(a.sigs, t.sigs);
@@ -2243,6 +2360,137 @@ int edv_merkle_append_batch_dev(uint64_t old_size, const uint8_t* d_old_hashes, 
   if ((err = launch_merkle(*cl.c, old_size, d_old_hashes, d_leaves, d_leaf_off, leaf_base, n, d_leaf_hashes,
                            d_node_hashes, d_new_hashes, d_root, s, d_roots, d_audit_paths)))
     return err;
+  if (!stream) HIPOK(hipStreamSynchronize(s), "stream sync");
+  return 0;
+}
+
+// Proof verification (row f-7).  What both forms of a call check before
+// anything is launched or written; *empty: n = 0, nothing to do.
+static int check_proof_args(uint64_t n, bool both_leaf_forms, std::initializer_list<const void*> required, bool* empty) {
+  *empty = n == 0;
+  if (n > EDV_MERKLE_MAX_LEAVES) return set_err(EDV_E_ARG, "merkle verify: more than EDV_MERKLE_MAX_LEAVES proofs");
+  if (both_leaf_forms) return set_err(EDV_E_ARG, "merkle verify: give leaves or leaf_hashes, not both");
+  if (n)
+    for (const void* p : required)
+      if (!p) return set_err(EDV_E_ARG, "merkle verify: null pointer");
+  return 0;
+}
+static int check_proof_align(std::initializer_list<const void*> words, std::initializer_list<const void*> hashes) {
+  for (const void* p : words)
+    if (reinterpret_cast<uintptr_t>(p) & 7) return set_err(EDV_E_ARG, "merkle verify: 64-bit arrays must be 8-byte aligned");
+  for (const void* p : hashes)
+    if (reinterpret_cast<uintptr_t>(p) & 15) return set_err(EDV_E_ARG, "merkle verify: hash buffers must be 16-byte aligned");
+  return 0;
+}
+
+int edv_merkle_verify_inclusion(const uint8_t* leaves, const uint64_t* leaf_off, const uint8_t* leaf_hashes,
+                                const uint64_t* leaf_index, const uint64_t* tree_size, const uint8_t* roots,
+                                const uint8_t* proofs, const uint64_t* proof_off, uint64_t n, uint8_t* status,
+                                uint8_t* computed, int device) {
+  g_err.clear();
+  int err;
+  bool empty;
+  if ((err = check_proof_args(n, leaves && leaf_hashes,
+                              {leaves ? static_cast<const void*>(leaves) : leaf_hashes, leaves ? leaf_off : proof_off,
+                               leaf_index, tree_size, roots, proofs, proof_off, status},
+                              &empty)))
+    return err;
+  if (empty) return 0;
+  if (leaves && (err = check_offsets(leaf_off, n))) return err;
+  if ((err = check_offsets(proof_off, n))) return err;
+  CtxLock cl(device);
+  if (cl.err) return cl.err;
+  memset(status, EDV_PROOF_UNVERIFIED, n);  // a call that fails part-way leaves rejections
+  return run_verify_inclusion_host(*cl.c, leaves, leaf_off, leaf_hashes, leaf_index, tree_size, roots, proofs, proof_off,
+                                   n, status, computed);
+}
+
+int edv_merkle_verify_inclusion_dev(const uint8_t* d_leaves, const uint64_t* d_leaf_off, uint64_t leaf_base,
+                                    const uint8_t* d_leaf_hashes, const uint64_t* d_leaf_index,
+                                    const uint64_t* d_tree_size, const uint8_t* d_roots, const uint8_t* d_proofs,
+                                    const uint64_t* d_proof_off, uint64_t proof_base, uint64_t n, uint8_t* d_status,
+                                    uint8_t* d_computed, int device, void* stream) {
+  g_err.clear();
+  int err;
+  bool empty;
+  if ((err = check_proof_args(n, d_leaves && d_leaf_hashes,
+                              {d_leaves ? static_cast<const void*>(d_leaves) : d_leaf_hashes,
+                               d_leaves ? d_leaf_off : d_proof_off, d_leaf_index, d_tree_size, d_roots, d_proofs,
+                               d_proof_off, d_status},
+                              &empty)))
+    return err;
+  // the lanes read sizes, indices and offsets as 64-bit words and every hash as two 16-byte vectors
+  if ((err = check_proof_align({d_leaf_off, d_leaf_index, d_tree_size, d_proof_off},
+                               {d_leaf_hashes, d_roots, d_proofs, d_computed})))
+    return err;
+  if (empty) return 0;
+  CtxLock cl(device);
+  if (cl.err) return cl.err;
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : cl.c->stream;
+  MerkleVerifyInclusion a;
+  a.n = n;
+  a.leaves = d_leaves;
+  a.leaf_off = d_leaf_off;
+  a.leaf_base = leaf_base;
+  a.leaf_hashes = reinterpret_cast<const uint32_t*>(d_leaf_hashes);
+  a.leaf_index = d_leaf_index;
+  a.tree_size = d_tree_size;
+  a.roots = reinterpret_cast<const uint32_t*>(d_roots);
+  a.proofs = reinterpret_cast<const uint32_t*>(d_proofs);
+  a.proof_off = d_proof_off;
+  a.proof_base = proof_base;
+  a.status = d_status;
+  a.computed = reinterpret_cast<uint32_t*>(d_computed);
+  HIPOK(launch_merkle_verify_inclusion_kernel(s, a), "merkle verify launch");
+  if (!stream) HIPOK(hipStreamSynchronize(s), "stream sync");
+  return 0;
+}
+
+int edv_merkle_verify_consistency(const uint64_t* old_size, const uint64_t* new_size, const uint8_t* old_roots,
+                                  const uint8_t* new_roots, const uint8_t* proofs, const uint64_t* proof_off, uint64_t n,
+                                  uint8_t* status, uint8_t* computed, int device) {
+  g_err.clear();
+  int err;
+  bool empty;
+  if ((err = check_proof_args(n, false, {old_size, new_size, old_roots, new_roots, proofs, proof_off, status}, &empty)))
+    return err;
+  if (empty) return 0;
+  if ((err = check_offsets(proof_off, n))) return err;
+  CtxLock cl(device);
+  if (cl.err) return cl.err;
+  memset(status, EDV_PROOF_UNVERIFIED, n);
+  return run_verify_consistency_host(*cl.c, old_size, new_size, old_roots, new_roots, proofs, proof_off, n, status,
+                                     computed);
+}
+
+int edv_merkle_verify_consistency_dev(const uint64_t* d_old_size, const uint64_t* d_new_size, const uint8_t* d_old_roots,
+                                      const uint8_t* d_new_roots, const uint8_t* d_proofs, const uint64_t* d_proof_off,
+                                      uint64_t proof_base, uint64_t n, uint8_t* d_status, uint8_t* d_computed,
+                                      int device, void* stream) {
+  g_err.clear();
+  int err;
+  bool empty;
+  if ((err = check_proof_args(n, false, {d_old_size, d_new_size, d_old_roots, d_new_roots, d_proofs, d_proof_off, d_status},
+                              &empty)))
+    return err;
+  if ((err = check_proof_align({d_old_size, d_new_size, d_proof_off}, {d_old_roots, d_new_roots, d_proofs, d_computed})))
+    return err;
+  if (empty) return 0;
+  CtxLock cl(device);
+  if (cl.err) return cl.err;
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : cl.c->stream;
+  MerkleVerifyConsistency a;
+  a.n = n;
+  a.old_size = d_old_size;
+  a.new_size = d_new_size;
+  a.old_roots = reinterpret_cast<const uint32_t*>(d_old_roots);
+  a.new_roots = reinterpret_cast<const uint32_t*>(d_new_roots);
+  a.proofs = reinterpret_cast<const uint32_t*>(d_proofs);
+  a.proof_off = d_proof_off;
+  a.proof_base = proof_base;
+  a.status = d_status;
+  a.computed = reinterpret_cast<uint32_t*>(d_computed);
+  HIPOK(launch_merkle_verify_consistency_kernel(s, a), "merkle verify launch");
   if (!stream) HIPOK(hipStreamSynchronize(s), "stream sync");
   return 0;
 }

@@ -99,6 +99,15 @@ def lib():
         h.edv_merkle_append_batch_dev.restype = ctypes.c_int
         h.edv_merkle_path_entries.argtypes = [u64, u64, ctypes.POINTER(u64)]
         h.edv_merkle_path_entries.restype = ctypes.c_int
+        h.edv_merkle_verify_inclusion.argtypes = [vp] * 8 + [u64, vp, vp, ctypes.c_int]
+        h.edv_merkle_verify_inclusion.restype = ctypes.c_int
+        h.edv_merkle_verify_inclusion_dev.argtypes = [vp, vp, u64, vp, vp, vp, vp, vp, vp, u64, u64, vp, vp,
+                                                      ctypes.c_int, vp]
+        h.edv_merkle_verify_inclusion_dev.restype = ctypes.c_int
+        h.edv_merkle_verify_consistency.argtypes = [vp] * 6 + [u64, vp, vp, ctypes.c_int]
+        h.edv_merkle_verify_consistency.restype = ctypes.c_int
+        h.edv_merkle_verify_consistency_dev.argtypes = [vp] * 6 + [u64, u64, vp, vp, ctypes.c_int, vp]
+        h.edv_merkle_verify_consistency_dev.restype = ctypes.c_int
         h.edv_verify_batch_dev_flags.argtypes = [vp, vp, vp, vp, u64, u64, vp, ctypes.c_int, vp, ctypes.c_uint32]
         h.edv_verify_batch_dev_flags.restype = ctypes.c_int
         h.edv_verify_batch_dev_pipelined.argtypes = [vp, vp, vp, vp, u64, u64, vp, ctypes.c_int, ctypes.c_uint32]
@@ -566,6 +575,109 @@ def merkle_append_batch_device(old_size, d_old_hashes, d_leaves, d_off, n, d_lea
     _check(lib().edv_merkle_append_batch_dev(old_size, d_old_hashes, d_leaves, d_off, leaf_base, n, d_leaf_hashes,
                                              d_node_hashes, d_new_hashes, d_root, d_roots, d_audit_paths, device,
                                              stream))
+
+
+# proof verification (row f-7): one status byte per proof, EDV_PROOF_* of include/edv.h
+PROOF_UNVERIFIED = 0   # never written by a kernel: what the host form fills the buffer with first
+PROOF_OK = 1
+PROOF_RANGE = 2        # leaf_index >= tree_size / old_size > new_size
+PROOF_SHORT = 3        # the walk needed an entry past the proof's end
+PROOF_LONG = 4         # inclusion only: entries left over after the walk
+PROOF_ROOT = 5         # the computed root (inclusion) / new root (consistency) differs
+PROOF_INCONSISTENT = 6  # consistency only: the new root matches and the old one does not
+
+
+def _u8(a, what, nbytes=None):
+    if not isinstance(a, np.ndarray):
+        a = np.frombuffer(bytes(a) or b"\0", dtype=np.uint8)
+    if a.dtype != np.uint8 or not a.flags.c_contiguous:
+        raise ValueError(what + " must be contiguous uint8")
+    if nbytes is not None and a.nbytes < nbytes:
+        raise ValueError(what + " is too small")
+    return a
+
+
+def _u64(a, what, count):
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    if a.ndim != 1 or len(a) != count:
+        raise ValueError("%s must hold %d entries" % (what, count))
+    return a
+
+
+def _proof_offsets(proof_off, proofs):
+    off = np.ascontiguousarray(proof_off, dtype=np.uint64)
+    if off.ndim != 1 or len(off) < 1:
+        raise ValueError("proof_off must hold n + 1 entries")
+    n = len(off) - 1
+    if n > MERKLE_MAX_LEAVES:
+        raise ValueError("more than MERKLE_MAX_LEAVES proofs in one call")
+    proofs = _u8(proofs, "proofs")
+    if 32 * int(off[-1]) > proofs.nbytes and int(off[-1]) > 0:
+        raise ValueError("proof_off exceeds the proof buffer")
+    return off, n, proofs
+
+
+def merkle_verify_inclusion(leaf_index, tree_size, roots, proofs, proof_off, leaves=None, leaf_off=None,
+                            leaf_hashes=None, want_computed=False, device: int = 0):
+    """n audit paths in one call (edv_merkle_verify_inclusion, row f-7).
+
+    proofs: packed 32-byte entries (bytes or uint8 array); proof_off: n + 1
+    offsets in entries; roots: n x 32 bytes; leaf_index / tree_size: n
+    integers below 2^64.  The leaves come as `leaves` (bytes laid out by the
+    n + 1 offsets `leaf_off`; the call stages them with the read-ahead the
+    kernel needs) or as `leaf_hashes` (n x 32 bytes), never both.  Returns (status, computed): n
+    PROOF_* bytes and the (n, 32) calculated roots (None unless wanted)."""
+    off, n, proofs = _proof_offsets(proof_off, proofs)
+    if (leaves is None) == (leaf_hashes is None):
+        raise ValueError("give leaves or leaf_hashes, not both")
+    idx, size = _u64(leaf_index, "leaf_index", n), _u64(tree_size, "tree_size", n)
+    roots = _u8(roots, "roots", 32 * n)
+    loff = None
+    if leaves is not None:
+        loff = _u64(leaf_off, "leaf_off", n + 1)
+        leaves = _u8(leaves, "leaves")
+        if int(loff[-1]) > leaves.nbytes:
+            raise ValueError("leaf_off exceeds the leaf buffer")
+    else:
+        leaf_hashes = _u8(leaf_hashes, "leaf_hashes", 32 * n)
+    status = np.zeros(n, dtype=np.uint8)
+    computed = np.zeros((n, 32), dtype=np.uint8) if want_computed else None
+    _check(lib().edv_merkle_verify_inclusion(_ptr(leaves), _ptr(loff), _ptr(leaf_hashes), idx.ctypes.data,
+                                             size.ctypes.data, roots.ctypes.data, proofs.ctypes.data, off.ctypes.data,
+                                             n, status.ctypes.data, _ptr(computed), device))
+    return status, computed
+
+
+def merkle_verify_inclusion_device(d_leaf_index, d_tree_size, d_roots, d_proofs, d_proof_off, n, d_status,
+                                   d_computed=None, d_leaves=None, d_leaf_off=None, d_leaf_hashes=None, device=0,
+                                   leaf_base=0, proof_base=0, stream=None):
+    """Device-resident form (pointers are ints, None = NULL); async on `stream` if given."""
+    _check(lib().edv_merkle_verify_inclusion_dev(d_leaves, d_leaf_off, leaf_base, d_leaf_hashes, d_leaf_index,
+                                                 d_tree_size, d_roots, d_proofs, d_proof_off, proof_base, n, d_status,
+                                                 d_computed, device, stream))
+
+
+def merkle_verify_consistency(old_size, new_size, old_roots, new_roots, proofs, proof_off, want_computed=False,
+                              device: int = 0):
+    """n consistency proofs in one call (edv_merkle_verify_consistency).
+    Returns (status, computed): n PROOF_* bytes and the (n, 64) calculated
+    old and new roots (None unless wanted)."""
+    off, n, proofs = _proof_offsets(proof_off, proofs)
+    old_size, new_size = _u64(old_size, "old_size", n), _u64(new_size, "new_size", n)
+    old_roots, new_roots = _u8(old_roots, "old_roots", 32 * n), _u8(new_roots, "new_roots", 32 * n)
+    status = np.zeros(n, dtype=np.uint8)
+    computed = np.zeros((n, 64), dtype=np.uint8) if want_computed else None
+    _check(lib().edv_merkle_verify_consistency(old_size.ctypes.data, new_size.ctypes.data, old_roots.ctypes.data,
+                                               new_roots.ctypes.data, proofs.ctypes.data, off.ctypes.data, n,
+                                               status.ctypes.data, _ptr(computed), device))
+    return status, computed
+
+
+def merkle_verify_consistency_device(d_old_size, d_new_size, d_old_roots, d_new_roots, d_proofs, d_proof_off, n,
+                                     d_status, d_computed=None, device=0, proof_base=0, stream=None):
+    """Device-resident form (pointers are ints, None = NULL); async on `stream` if given."""
+    _check(lib().edv_merkle_verify_consistency_dev(d_old_size, d_new_size, d_old_roots, d_new_roots, d_proofs,
+                                                   d_proof_off, proof_base, n, d_status, d_computed, device, stream))
 
 
 def verify_detached_batch(items, device_mask: int = 0):

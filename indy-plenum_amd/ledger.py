@@ -10,6 +10,8 @@ classes, written from their semantics:
   plenum/common/ledger.py:34-53           appendTxns (uncommittedTree, uncommittedRootHash)
   plenum/common/ledger.py:71-96           commitTxns: txn.update(self.append(txn)) per txn
   plenum/common/ledger.py:98-137          discardTxns, treeWithAppliedTxns
+  plenum/client/client.py:846-873         verifyMerkleProof -> verify_merkle_proofs (row f-7)
+  plenum/common/ledger_manager.py:564-609 hasValidCatchupReplies -> Ledger.verify_catchup_txns
 
 commitTxns(count) is one CompactMerkleTree.append_batch call
 (edv_merkle_append_batch from merkle.MIN_DEVICE_APPEND_LEAVES transactions
@@ -25,11 +27,40 @@ class never looks inside a transaction, it only `update`s the committed ones
 from copy import copy
 
 from . import base58
-from .merkle import CompactMerkleTree, ConsistencyVerificationFailed
+from .merkle import STH, CompactMerkleTree, ConsistencyVerificationFailed, MerkleVerifier
+
+MERKLE_KEYS = ("auditPath", "seqNo", "rootHash")  # what a committed transaction carries beyond what was hashed
 
 
 def _bytes_as_they_are(txn):
     return txn.encode() if isinstance(txn, str) else bytes(txn)
+
+
+def _as_hash(h):
+    return base58.b58decode(h) if isinstance(h, str) else bytes(h)
+
+
+def verify_merkle_proofs(results, serialize_for_tree=None, on_device=None, device=0):
+    """Check the Merkle proof every result carries, all in one batched call
+    (row f-7; plenum/client/client.py:846-873, verifyMerkleProof, one
+    verify_leaf_inclusion per reply there).  A result is a dict with `seqNo`,
+    `rootHash` and `auditPath`, base58 as Ledger.commitTxns writes them; its
+    leaf is serialize_for_tree of the result without those three keys (pass
+    the ledger's own serializer: the default, as Ledger's, takes the
+    transaction to be the bytes, which a dict is not), at index seqNo - 1 of
+    the tree of seqNo leaves.  Returns True, or raises the first failing
+    entry's exception (ValueError, ProofError)."""
+    results = list(results)
+    serialize = serialize_for_tree or _bytes_as_they_are
+    leaves, indices, proofs, sths = [], [], [], []
+    for r in results:
+        seqNo = int(r["seqNo"])
+        leaves.append(serialize({k: v for k, v in r.items() if k not in MERKLE_KEYS}))
+        indices.append(seqNo - 1)
+        proofs.append([_as_hash(a) for a in r["auditPath"]])
+        sths.append(STH(tree_size=seqNo, sha256_root_hash=_as_hash(r["rootHash"])))
+    return MerkleVerifier().verify_leaf_inclusion_batch(leaves, indices, proofs, sths, on_device=on_device,
+                                                        device=device).raise_first()
 
 
 class Ledger:
@@ -185,6 +216,22 @@ class Ledger:
         tempTree = copy(currentTree)
         tempTree.extend([self.serialize_for_tree(t) for t in txns], on_device=self.on_device, device=self.device)
         return tempTree
+
+    def verify_catchup_txns(self, txns, final_size, final_root_hash, proof):
+        """Do `txns`, applied to the committed tree, lead to a tree consistent
+        with the one of final_size leaves and final_root_hash (the check of
+        plenum/common/ledger_manager.py:564-609)?  The temporary tree is one
+        extend (on the device by batch size); the consistency proof is a
+        single one, so it is walked on the host.  final_root_hash and the
+        proof's entries are base58 strings or bytes.  Any exception means
+        False, as in the reference."""
+        try:
+            tempTree = self.treeWithAppliedTxns(txns)
+            return bool(MerkleVerifier().verify_tree_consistency(
+                tempTree.tree_size, int(final_size), tempTree.root_hash, _as_hash(final_root_hash),
+                [_as_hash(p) for p in proof]))
+        except Exception:
+            return False
 
     def reset_uncommitted(self):
         self.uncommittedTxns = []

@@ -21,9 +21,17 @@ returns (ledger/ledger.py:145-155: the audit path, and the root hash read after
 it), one edv_merkle_append_batch call per batch (kernel
 edv_merkle_append_kernel after the extend's): what `Ledger.commitTxns`
 (ledger.py) needs for a 3PC batch.
+
+`MerkleVerifier` (row f-7; ledger/merkle_verifier.py) checks such proofs: the
+reference's single calls on the host, and batches of audit paths or
+consistency proofs in one edv_merkle_verify_inclusion /
+edv_merkle_verify_consistency call, one lane per proof, returning a
+ProofVerdicts.  `verify_append_batch` hands an AppendBatch's packed paths and
+roots to the device as they are.
 """
 import hashlib
 from binascii import hexlify
+from collections import namedtuple
 
 import numpy as np
 
@@ -45,8 +53,32 @@ MIN_DEVICE_LEAVES = 256
 MIN_DEVICE_APPEND_LEAVES = 256
 
 
+# MerkleVerifier.*_batch(on_device=None) takes the device from this many proofs
+# on: the smallest size measured, at which verify_append_batch on the device
+# already beats the host walk on both trees (profiles/r09/merkle_verify_bench.json,
+# "crossover": 153 us against 185 us for the 64 appends onto an empty tree,
+# paths of 3 entries, the narrowest margin of the table, and 169 us against
+# 332 us onto 2^20 + 12,345 leaves; nothing below 64 was measured)
+MIN_DEVICE_VERIFY_PROOFS = 64
+
+
 class ConsistencyVerificationFailed(Exception):
     pass
+
+
+STH = namedtuple("STH", ["tree_size", "sha256_root_hash"])
+
+
+class VerifyError(Exception):
+    """A proof did not verify."""
+
+
+class ProofError(VerifyError):
+    """The proof is invalid: too short, too long, or it arrives at another root."""
+
+
+class ConsistencyError(VerifyError):
+    """The proof shows that the two trees are inconsistent."""
 
 
 def _popcount(x):
@@ -462,3 +494,293 @@ class CompactMerkleTree:
     def reset(self):
         self.__hashStore.reset()
         self._update(0, ())
+
+
+# ---- proof verification (row f-7)
+_U64 = 1 << 64
+_ZERO32 = b"\0" * 32
+
+
+def _walk_inclusion(hasher, leaf_hash, leaf_index, tree_size, path, root):
+    """One audit path (RFC 6962 section 2.1.1) -> (status, calculated root or
+    32 zero bytes): the walk of edv_merkle.h in hashlib."""
+    if not 0 <= leaf_index < tree_size < _U64:
+        return edv.PROOF_RANGE, _ZERO32
+    node, last, used, acc = leaf_index, tree_size - 1, 0, leaf_hash
+    while last > 0:
+        if node & 1 or node < last:
+            if used == len(path):
+                return edv.PROOF_SHORT, _ZERO32
+            acc = hasher.hash_children(path[used], acc) if node & 1 else hasher.hash_children(acc, path[used])
+            used += 1
+        node >>= 1
+        last >>= 1
+    if used != len(path):
+        return edv.PROOF_LONG, acc
+    return (edv.PROOF_OK if acc == root else edv.PROOF_ROOT), acc
+
+
+def _walk_consistency(hasher, old_size, new_size, old_root, new_root, proof):
+    """One consistency proof (RFC 6962 section 2.1.2) -> (status, calculated
+    old root + new root, or 64 zero bytes where no walk is made)."""
+    none = _ZERO32 + _ZERO32
+    if old_size < 0 or new_size < 0 or old_size >= _U64 or new_size >= _U64 or old_size > new_size:
+        return edv.PROOF_RANGE, none
+    if old_size == new_size:
+        return (edv.PROOF_OK if old_root == new_root else edv.PROOF_INCONSISTENT), none
+    if old_size == 0:
+        return edv.PROOF_OK, none
+    node, last, used = old_size - 1, new_size - 1, 0
+    while node & 1:
+        node >>= 1
+        last >>= 1
+    if node:
+        if not proof:
+            return edv.PROOF_SHORT, none
+        old = new = proof[0]
+        used = 1
+    else:
+        old = new = old_root
+    while last > 0:
+        if node & 1 or node < last:
+            if used == len(proof):
+                return edv.PROOF_SHORT, none
+            if node & 1:
+                old = hasher.hash_children(proof[used], old)
+                new = hasher.hash_children(proof[used], new)
+            else:
+                new = hasher.hash_children(new, proof[used])
+            used += 1
+        node >>= 1
+        last >>= 1
+    if new != new_root:
+        return edv.PROOF_ROOT, old + new
+    return (edv.PROOF_OK if old == old_root else edv.PROOF_INCONSISTENT), old + new
+
+
+class ProofVerdicts:
+    """What a batched verification returned: `status`, a uint8 array of
+    edv.PROOF_* (one per proof), `ok`, the same as bools, and `computed`, the
+    calculated roots ((n, 32); consistency (n, 64): old, then new) when asked
+    for, else None.  len() and iteration (bools) as a list of verdicts;
+    raise_for(i) raises what the single call raises for entry i."""
+
+    def __init__(self, status, computed=None):
+        self.status = np.asarray(status, dtype=np.uint8)
+        self.ok = self.status == edv.PROOF_OK
+        self.computed = computed
+
+    def __len__(self):
+        return len(self.status)
+
+    def __iter__(self):
+        return iter(bool(x) for x in self.ok)
+
+    def raise_for(self, i):
+        """True for an accepted proof; else the single call's exception:
+        ValueError (sizes out of range), ProofError, ConsistencyError."""
+        st = int(self.status[i])
+        if st == edv.PROOF_OK:
+            return True
+        if st == edv.PROOF_RANGE:
+            raise ValueError("proof %d: leaf index not below the tree size, or the older tree is the bigger one" % i)
+        if st == edv.PROOF_SHORT:
+            raise ProofError("proof %d is too short" % i)
+        if st == edv.PROOF_LONG:
+            raise ProofError("proof %d is too long" % i)
+        if st == edv.PROOF_ROOT:
+            raise ProofError("proof %d: constructed root hash differs from the provided root hash" % i)
+        if st == edv.PROOF_INCONSISTENT:
+            raise ConsistencyError("proof %d: inconsistency: first root hash does not match" % i)
+        raise VerifyError("proof %d was not verified" % i)
+
+    def raise_first(self):
+        """True if every proof is accepted, else the first failing entry's exception."""
+        bad = np.flatnonzero(~self.ok)
+        return self.raise_for(int(bad[0])) if len(bad) else True
+
+
+def _hash32(h, what):
+    h = bytes(h)
+    if len(h) != 32:
+        raise ValueError("%s must be 32 bytes" % what)
+    return h
+
+
+def _pack_proofs(proofs):
+    """list of lists of 32-byte hashes -> ((entries, 32) uint8 array, n + 1 offsets in entries)."""
+    off = np.zeros(len(proofs) + 1, dtype=np.uint64)
+    flat = []
+    for i, p in enumerate(proofs):
+        flat.extend(_hash32(h, "a proof entry") for h in p)
+        off[i + 1] = len(flat)
+    return np.frombuffer(b"".join(flat), dtype=np.uint8).reshape(-1, 32), off
+
+
+def _in_u64(x):
+    return 0 <= x < _U64
+
+
+class MerkleVerifier:
+    """The reference's ledger/merkle_verifier.py by name, call shape, return
+    value and exception, written from RFC 6962 sections 2.1.1 and 2.1.2; and
+    the same checks for a batch of proofs in one device call (gfx950 kernels
+    edv_merkle_verify_inclusion_kernel / edv_merkle_verify_consistency_kernel).
+    A single proof is at most 64 node hashes: always on the host."""
+
+    def __init__(self, hasher=None):
+        self.hasher = hasher or TreeHasher()
+
+    def __repr__(self):
+        return "%r(hasher: %r)" % (self.__class__.__name__, self.hasher)
+
+    # ---- single proofs (host)
+    def verify_tree_consistency(self, old_tree_size, new_tree_size, old_root, new_root, proof):
+        st, _ = _walk_consistency(self.hasher, int(old_tree_size), int(new_tree_size), bytes(old_root),
+                                  bytes(new_root), [bytes(h) for h in proof])
+        return ProofVerdicts([st]).raise_for(0)
+
+    def verify_leaf_hash_inclusion(self, leaf_hash, leaf_index, proof, sth):
+        st, _ = _walk_inclusion(self.hasher, bytes(leaf_hash), int(leaf_index), int(sth.tree_size),
+                                [bytes(h) for h in proof], bytes(sth.sha256_root_hash))
+        return ProofVerdicts([st]).raise_for(0)
+
+    def verify_leaf_inclusion(self, leaf, leaf_index, proof, sth):
+        return self.verify_leaf_hash_inclusion(self.hasher.hash_leaf(leaf), leaf_index, proof, sth)
+
+    @classmethod
+    def audit_path_length(cls, index, tree_size):
+        length, last = 0, tree_size - 1
+        while last > 0:
+            if index & 1 or index < last:
+                length += 1
+            index >>= 1
+            last >>= 1
+        return length
+
+    # ---- batches
+    def _device_default(self, n, on_device):
+        if on_device is None:
+            on_device = n >= MIN_DEVICE_VERIFY_PROOFS
+        if on_device and self.hasher.hashfunc is not hashlib.sha256:
+            raise ValueError("the device verifies SHA-256 trees only")
+        return on_device
+
+    def _inclusion(self, leaves, leaf_hashes, leaf_indices, sizes, roots, paths, off, on_device, device, want_computed,
+                   max_call=None):
+        """leaves: list of bytes, or None with leaf_hashes an (n, 32) array;
+        roots (n, 32), paths (entries, 32) and off (n + 1, in entries) are the
+        packed arrays the device call takes as they are."""
+        n = len(off) - 1
+        idx, size = [int(x) for x in leaf_indices], [int(x) for x in sizes]
+        given = len(leaves) if leaf_hashes is None else len(leaf_hashes)
+        if not len(idx) == len(size) == len(roots) == given == n:
+            raise ValueError("leaves, leaf indices, proofs and tree heads differ in number")
+        status = np.zeros(n, dtype=np.uint8)
+        computed = np.zeros((n, 32), dtype=np.uint8) if want_computed else None
+        if not self._device_default(n, on_device):
+            pb, rb = paths.tobytes(), roots.tobytes()
+            for i in range(n):
+                lo, hi = 32 * int(off[i]), 32 * int(off[i + 1])
+                lh = self.hasher.hash_leaf(leaves[i]) if leaf_hashes is None else leaf_hashes[i].tobytes()
+                st, comp = _walk_inclusion(self.hasher, lh, idx[i], size[i], [pb[k:k + 32] for k in range(lo, hi, 32)],
+                                           rb[32 * i:32 * i + 32])
+                status[i] = st
+                if want_computed:
+                    computed[i] = np.frombuffer(comp, dtype=np.uint8)
+            return ProofVerdicts(status, computed)
+        # integers the C-ABI cannot carry are out of range whatever the proof says
+        fits = [_in_u64(a) and _in_u64(b) for a, b in zip(idx, size)]
+        idx_a = np.array([a if f else 0 for a, f in zip(idx, fits)], dtype=np.uint64)
+        size_a = np.array([b if f else 0 for b, f in zip(size, fits)], dtype=np.uint64)
+        step = edv.MERKLE_MAX_LEAVES if max_call is None else int(max_call)
+        if step < 1 or step > edv.MERKLE_MAX_LEAVES:
+            raise ValueError("max_call must be in [1, %d]" % edv.MERKLE_MAX_LEAVES)
+        for lo in range(0, n, step):
+            hi = min(n, lo + step)
+            kw = {}
+            if leaf_hashes is None:
+                loff = np.zeros(hi - lo + 1, dtype=np.uint64)
+                loff[1:] = np.cumsum([len(x) for x in leaves[lo:hi]], dtype=np.uint64)
+                kw = dict(leaves=np.frombuffer(b"".join(leaves[lo:hi]) + b"\0" * 8, dtype=np.uint8), leaf_off=loff)
+            else:
+                kw = dict(leaf_hashes=np.ascontiguousarray(leaf_hashes[lo:hi]))
+            st, comp = edv.merkle_verify_inclusion(idx_a[lo:hi], size_a[lo:hi], np.ascontiguousarray(roots[lo:hi]),
+                                                   paths, off[lo:hi + 1], want_computed=want_computed, device=device,
+                                                   **kw)
+            status[lo:hi] = st
+            if want_computed:
+                computed[lo:hi] = comp
+        return ProofVerdicts(status, computed)
+
+    @staticmethod
+    def _heads(sths):
+        sths = list(sths)
+        roots = np.frombuffer(b"".join(_hash32(s.sha256_root_hash, "a root hash") for s in sths),
+                              dtype=np.uint8).reshape(-1, 32)
+        return [s.tree_size for s in sths], roots
+
+    def verify_leaf_inclusion_batch(self, leaves, leaf_indices, proofs, sths, on_device=None, device=0,
+                                    want_computed=False):
+        """verify_leaf_inclusion for every (leaf, leaf_index, proof, sth), as a
+        ProofVerdicts; one edv_merkle_verify_inclusion call from
+        MIN_DEVICE_VERIFY_PROOFS proofs on (on_device None), else the same
+        walk in hashlib."""
+        sizes, roots = self._heads(sths)
+        paths, off = _pack_proofs(list(proofs))
+        return self._inclusion([bytes(x) for x in leaves], None, list(leaf_indices), sizes, roots, paths, off,
+                               on_device, device, want_computed)
+
+    def verify_leaf_hash_inclusion_batch(self, leaf_hashes, leaf_indices, proofs, sths, on_device=None, device=0,
+                                         want_computed=False):
+        sizes, roots = self._heads(sths)
+        paths, off = _pack_proofs(list(proofs))
+        lh = np.frombuffer(b"".join(_hash32(h, "a leaf hash") for h in leaf_hashes), dtype=np.uint8).reshape(-1, 32)
+        return self._inclusion(None, lh, list(leaf_indices), sizes, roots, paths, off, on_device, device, want_computed)
+
+    def verify_tree_consistency_batch(self, items, on_device=None, device=0, want_computed=False):
+        """items: (old_tree_size, new_tree_size, old_root, new_root, proof)
+        each, the arguments of verify_tree_consistency."""
+        items = [(int(a), int(b), _hash32(ra, "a root hash"), _hash32(rb, "a root hash"), list(p))
+                 for a, b, ra, rb, p in items]
+        n = len(items)
+        if not self._device_default(n, on_device):
+            res = [_walk_consistency(self.hasher, a, b, ra, rb, [_hash32(h, "a proof entry") for h in p])
+                   for a, b, ra, rb, p in items]
+            computed = None
+            if want_computed:
+                computed = np.frombuffer(b"".join(c for _, c in res), dtype=np.uint8).reshape(-1, 64)
+            return ProofVerdicts([st for st, _ in res], computed)
+        proofs, off = _pack_proofs([p for *_, p in items])
+        fits = [_in_u64(a) and _in_u64(b) for a, b, *_ in items]
+        # sizes the C-ABI cannot carry go in as (1, 0): out of range
+        old = np.array([it[0] if f else 1 for it, f in zip(items, fits)], dtype=np.uint64)
+        new = np.array([it[1] if f else 0 for it, f in zip(items, fits)], dtype=np.uint64)
+        status, computed = edv.merkle_verify_consistency(old, new, b"".join(it[2] for it in items),
+                                                         b"".join(it[3] for it in items), proofs, off,
+                                                         want_computed=want_computed, device=device)
+        return ProofVerdicts(status, computed)
+
+    def verify_append_batch(self, old_size, leaves, batch, on_device=None, device=0, max_call=None,
+                            want_computed=False):
+        """Check what append_batch returned for `leaves` appended to a tree of
+        old_size leaves: leaf i has index old_size + i in the tree of
+        old_size + i + 1 leaves, whose root is batch.roots[i]; its audit path
+        (smallest subtree first: the verifier's order, lowest level first) is
+        read where the AppendBatch holds it, packed, with no repacking."""
+        leaves = [bytes(x) for x in leaves]
+        n = len(leaves)
+        if n != len(batch) or int(old_size) != batch.old_size:
+            raise ValueError("the AppendBatch is not that of these leaves")
+        off = np.zeros(n + 1, dtype=np.uint64)   # leaf i's path has popcount(old_size + i) entries
+        off[1:] = np.cumsum([_popcount(batch.old_size + i) for i in range(n)], dtype=np.uint64)
+        if int(off[-1]) != len(batch.paths):
+            raise ValueError("the AppendBatch's packed paths do not match its sizes")
+        idx = [batch.old_size + i for i in range(n)]
+        return self._inclusion(leaves, None, idx, [s + 1 for s in idx], np.ascontiguousarray(batch.roots),
+                               np.ascontiguousarray(batch.paths), off, on_device, device, want_computed, max_call)
+
+
+def verify_append_batch(old_size, leaves, batch, on_device=None, device=0, max_call=None):
+    """MerkleVerifier().verify_append_batch: the verdicts on an AppendBatch."""
+    return MerkleVerifier().verify_append_batch(old_size, leaves, batch, on_device, device, max_call)

@@ -26,6 +26,20 @@ efficiency (mean over the waves of mean / max trip count of the fold, from the
 sizes alone).  The smallest size from which (c) beats (e) on both trees is
 MIN_DEVICE_APPEND_LEAVES (indy_plenum_amd/merkle.py).
 
+With --leg verify: batched proof verification (row f-7), written to
+profiles/r09/merkle_verify_bench.json.  For 64 ... 65,536 proofs, the audit
+paths and roots the batched append returns for that many leaves of 256 bytes
+onto old = 0 and old = 2^20 + 12,345:
+  a  edv_merkle_verify_inclusion_dev  device-resident, on the append's own device outputs: leaf hashes,
+                                      and leaf bytes (the lanes hash their leaves)
+  b  edv_merkle_verify_inclusion      host buffers, leaf bytes (staging and copies included)
+  c  MerkleVerifier.verify_append_batch(on_device=True)    (b) with the Python shim's packing
+  e  MerkleVerifier.verify_append_batch(on_device=False)   the host walk in hashlib
+with the entries per proof and the lane efficiency of the walk (mean / max
+trip count per wave).  The smallest size from which (c) beats (e) on both
+trees is MIN_DEVICE_VERIFY_PROOFS.  And 10,000 consistency proofs (m, 4096)
+of one real tree, verify_tree_consistency_batch on the device and on the host.
+
 Every figure is wall clock around calls that end in a device synchronise (the
 device forms with stream = NULL synchronise the library stream before they
 return), the median of 5 repetitions after a warm-up; a repetition repeats
@@ -173,21 +187,119 @@ def append_leg(args, rng):
     return res
 
 
+VERIFY_SIZES = (64, 100, 256, 1000, 10000, 65536)
+
+
+def verify_leg(args, rng):
+    """Batched proof verification against the host walk (module docstring)."""
+    res = {"leaf_bytes": LEAF_BYTES, "window_s": args.window, "version": edv.version(), "rows": []}
+    blob = rng.integers(0, 256, N_BIG * LEAF_BYTES + 8, dtype=np.uint8)
+    off = np.arange(N_BIG + 1, dtype=np.uint64) * np.uint64(LEAF_BYTES)
+    leaves = [blob[i * LEAF_BYTES:(i + 1) * LEAF_BYTES].tobytes() for i in range(N_BIG)]
+    d_blob, d_off = dev(blob), dev(off)
+    v = merkle.MerkleVerifier()
+    for old in OLDS:
+        fr = frontier(rng, old)
+        frl = [fr[i:i + 32].tobytes() for i in range(0, len(fr), 32)]
+        d_old = dev(fr) if old else None
+        for n in VERIFY_SIZES:
+            entries = edv.merkle_path_entries(old, n)
+            d_lh, d_new, d_root = edv.DeviceBuffer(32 * n), edv.DeviceBuffer(32 * 64), edv.DeviceBuffer(32)
+            d_roots, d_paths = edv.DeviceBuffer(32 * n), edv.DeviceBuffer(32 * max(1, entries))
+            # the proofs: what the batched append wrote, on the device and (the host loop's) on the host
+            edv.merkle_append_batch_device(old, d_old.ptr if d_old else None, d_blob.ptr, d_off.ptr, n, d_lh.ptr, None,
+                                           d_new.ptr, d_root.ptr, d_roots.ptr, d_paths.ptr, device=args.device)
+            t = merkle.CompactMerkleTree(tree_size=old, hashes=frl)
+            sub_leaves = leaves[:n]
+            batch = t.append_batch(sub_leaves, on_device=False)
+            poff = np.array([merkle.popcount_prefix(old + i) - merkle.popcount_prefix(old) for i in range(n + 1)],
+                            dtype=np.uint64)
+            idx = np.arange(old, old + n, dtype=np.uint64)
+            size = idx + np.uint64(1)
+            d_poff, d_idx, d_size = dev(poff), dev(idx), dev(size)
+            d_status = edv.DeviceBuffer(n)
+            sub_blob, sub_off = blob[:n * LEAF_BYTES + 8], off[:n + 1]
+            roots, paths = np.ascontiguousarray(batch.roots), np.ascontiguousarray(batch.paths)
+
+            def a_hashes():
+                edv.merkle_verify_inclusion_device(d_idx.ptr, d_size.ptr, d_roots.ptr, d_paths.ptr, d_poff.ptr, n,
+                                                   d_status.ptr, d_leaf_hashes=d_lh.ptr, device=args.device)
+
+            def a_leaves():
+                edv.merkle_verify_inclusion_device(d_idx.ptr, d_size.ptr, d_roots.ptr, d_paths.ptr, d_poff.ptr, n,
+                                                   d_status.ptr, d_leaves=d_blob.ptr, d_leaf_off=d_off.ptr,
+                                                   device=args.device)
+
+            def b():
+                return edv.merkle_verify_inclusion(idx, size, roots, paths, poff, leaves=sub_blob, leaf_off=sub_off,
+                                                   device=args.device)
+
+            def c():
+                return v.verify_append_batch(old, sub_leaves, batch, on_device=True, device=args.device)
+
+            def e():
+                return v.verify_append_batch(old, sub_leaves, batch, on_device=False)
+
+            # results first: every route accepts every proof
+            for fn in (a_hashes, a_leaves):
+                d_status.upload(np.zeros(n, np.uint8))
+                fn()
+                assert (d_status.download() == edv.PROOF_OK).all()
+            assert (b()[0] == edv.PROOF_OK).all() and c().ok.all() and e().ok.all()
+            trips = np.array([bin(old + i).count("1") for i in range(n)], dtype=np.float64)
+            eff = float(np.mean([w.mean() / w.max() if w.max() else 1.0
+                                 for w in (trips[lo:lo + 64] for lo in range(0, n, 64))]))
+            row = {"old": old, "n": n, "path_entries_per_proof": entries / n, "lane_efficiency": eff,
+                   "a_verify_dev_leaf_hashes": timed(a_hashes, args.window),
+                   "a_verify_dev_leaf_bytes": timed(a_leaves, args.window),
+                   "b_verify_host_buffers": timed(b, args.window),
+                   "c_verify_append_batch_device": timed(c, args.window),
+                   "e_verify_append_batch_host_walk": timed(e, args.window)}
+            row["c_beats_e"] = (row["c_verify_append_batch_device"]["median_us"]
+                                < row["e_verify_append_batch_host_walk"]["median_us"])
+            res["rows"].append(row)
+            print(json.dumps(row), flush=True)
+    cross = None
+    for n in sorted(VERIFY_SIZES, reverse=True):
+        if all(r["c_beats_e"] for r in res["rows"] if r["n"] == n):
+            cross = n
+        else:
+            break
+    res["crossover"] = {"min_device_verify_proofs": cross,
+                        "rule": "smallest measured n from which c < e for every old, at n and every larger n"}
+    # consistency: 10,000 proofs (m, 4096) from one real tree, device-resident and host buffers against the host walk
+    t = merkle.CompactMerkleTree()
+    t.extend(leaves[:4096], on_device=False)
+    ms = [1 + (k * 37) % 4095 for k in range(10000)]
+    items = [(m, 4096, t.merkle_tree_hash(0, m), t.root_hash, t.consistency_proof(m, 4096)) for m in ms]
+    assert v.verify_tree_consistency_batch(items, on_device=True).ok.all()
+    assert v.verify_tree_consistency_batch(items, on_device=False).ok.all()
+    res["consistency"] = {"n": len(items), "new_size": 4096,
+                          "entries_per_proof": sum(len(it[4]) for it in items) / len(items),
+                          "batch_device": timed(lambda: v.verify_tree_consistency_batch(
+                              items, on_device=True, device=args.device), args.window),
+                          "batch_host_walk": timed(lambda: v.verify_tree_consistency_batch(items, on_device=False),
+                                                   args.window)}
+    print(json.dumps(res["consistency"]), flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=("extend", "append"), default="extend")
+    ap.add_argument("--leg", choices=("extend", "append", "verify"), default="extend")
     ap.add_argument("--out", default=None)
     ap.add_argument("--window", type=float, default=0.2)
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "r07", "merkle_bench.json") if args.leg == "extend" else \
-            os.path.join(ROOT, "profiles", "r08", "merkle_append_bench.json")
+        args.out = {"extend": os.path.join(ROOT, "profiles", "r07", "merkle_bench.json"),
+                    "append": os.path.join(ROOT, "profiles", "r08", "merkle_append_bench.json"),
+                    "verify": os.path.join(ROOT, "profiles", "r09", "merkle_verify_bench.json")}[args.leg]
     if edv.device_count() < 1:
         sys.exit("bench_merkle needs a gfx950 GPU")
     rng = np.random.default_rng(0x6962)
-    if args.leg == "append":
-        res = append_leg(args, rng)
+    if args.leg in ("append", "verify"):
+        res = append_leg(args, rng) if args.leg == "append" else verify_leg(args, rng)
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump(res, f, indent=1)
