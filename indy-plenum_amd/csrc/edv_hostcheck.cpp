@@ -546,6 +546,18 @@ void hc_trim_limits(uint64_t keep, uint64_t chunk, uint64_t* out13) {
                           t.slot_off, t.packed, t.blob, t.stage, t.acc_host, t.dig_host};
   memcpy(out13, v, sizeof v);
 }
+// the Merkle buffers' sizes, out: one row of kMerkleBufs = 15 in MerkleBuf's order (no Merkle limit depends on the chunk)
+static void put_sizes(uint64_t* out15, const MerkleSizes& s) { memcpy(out15, s.data(), sizeof s); }
+void hc_merkle_extend_needs(uint64_t old_size, uint64_t n, uint64_t mbytes, int host_form, int want_leaf, int want_node,
+                            int want_roots, int want_paths, uint64_t* out15) {
+  put_sizes(out15, merkle_extend_needs(old_size, n, mbytes, host_form, want_leaf, want_node, want_roots, want_paths));
+}
+void hc_merkle_verify_needs(int inclusion, uint64_t n, uint64_t lbytes, uint64_t entries, int want_computed, uint64_t* out15) {
+  put_sizes(out15, merkle_verify_needs(inclusion, n, lbytes, entries, want_computed));
+}
+void hc_merkle_trim_limits(uint64_t keep, uint64_t* out15) {
+  put_sizes(out15, merkle_trim_limits(keep, trim_limits(keep, uint64_t(1) << 18)));
+}
 // the known answers of edv_self_test (edv_selftest_cases.h), as the library holds them
 int hc_selftest_count() { return kSelfTestCases; }
 int hc_selftest_case(int i, uint8_t* sig64, uint8_t* pk32, uint8_t* msg, uint64_t* mlen, int* accept, int* rule) {
@@ -641,22 +653,12 @@ int hc_merkle_extend(uint64_t old_size, const uint8_t* old_hashes, const uint8_t
   if (old_size) memcpy(oldw.data(), old_hashes, 32 * size_t(popc64(old_size)));
   std::vector<uint32_t> leafw(leaf_hashes ? 8 * n : 0), nodew(node_hashes ? 8 * nodes : 0);
   std::vector<uint32_t> roots(8 * merkle_scratch_hashes(old_size, new_size) + 8);
-  MerklePass a;
-  a.old_size = old_size;
-  a.new_size = new_size;
-  a.old_hashes = oldw.data();
-  a.leaf_out = leaf_hashes ? leafw.data() : nullptr;
-  a.node_out = node_hashes ? nodew.data() : nullptr;
-  a.new_hashes = neww.data();
-  a.in = nullptr;
-  uint32_t* rp = roots.data();
+  MerklePass args = merkle_pass_args(old_size, new_size, oldw.data(), leaf_hashes ? leafw.data() : nullptr,
+                                     node_hashes ? nodew.data() : nullptr, neww.data());
   std::vector<uint32_t> lvl0(8 * kMerkleT), lvl1(8 * kMerkleT);
   uint32_t* lvl[2] = {lvl0.data(), lvl1.data()};
-  for (int h0 = 0; merkle_pass_runs(old_size, new_size, h0); h0 += kMerkleLogT) {
-    const uint64_t next_items =
-        merkle_pass_runs(old_size, new_size, h0 + kMerkleLogT) ? merkle_pass_items(old_size, new_size, h0 + kMerkleLogT) : 0;
-    a.h0 = h0;
-    a.roots_out = next_items ? rp : nullptr;
+  merkle_for_each_pass(old_size, new_size, roots.data(), args, [&](const MerklePass& a) {  // the runtime's schedule
+    const int h0 = a.h0;
     const uint64_t tile0 = merkle_pass_first_tile(old_size, h0), tiles = merkle_pass_tiles(old_size, new_size, h0);
     for (uint64_t tile = tile0; tile < tile0 + tiles; tile++) {
       for (uint32_t w = 0; w < 8 * kMerkleT; w++) lvl0[w] = lvl1[w] = 0xDEADBEEFu;  // nothing stale may be read
@@ -676,10 +678,9 @@ int hc_merkle_extend(uint64_t old_size, const uint8_t* old_hashes, const uint8_t
         for (uint32_t j = 0; j < (uint32_t(kMerkleT) >> hl); j++)
           merkle_level(a, tile, hl, j, lvl[(hl - 1) & 1], lvl[hl & 1]);
     }
-    a.in = rp;
-    rp += 8 * next_items;
-  }
-  merkle_finish(old_size, new_size, a.old_hashes, a.new_hashes, rootw.data());
+    return 0;
+  });
+  merkle_finish(old_size, new_size, args.old_hashes, args.new_hashes, rootw.data());
   if (leaf_hashes && n) memcpy(leaf_hashes, leafw.data(), 32 * n);
   if (node_hashes && nodes) memcpy(node_hashes, nodew.data(), 32 * nodes);
   memcpy(new_hashes, neww.data(), 32 * size_t(popc64(new_size)));
@@ -709,15 +710,8 @@ int hc_merkle_append_batch(uint64_t old_size, const uint8_t* old_hashes, const u
   if (old_size) memcpy(oldw.data(), old_hashes, 32 * size_t(popc64(old_size)));
   memcpy(leafw.data(), lhp, 32 * n);
   if (nodes) memcpy(nodew.data(), nhp, 32 * nodes);
-  MerkleAppend a;
-  a.old_size = old_size;
-  a.n = n;
-  a.path_base = merkle_popc_prefix(old_size);
-  a.old_hashes = oldw.data();
-  a.leaf_hashes = leafw.data();
-  a.node_hashes = nodew.data();
-  a.roots = roots ? rootsw.data() : nullptr;
-  a.paths = audit_paths ? pathsw.data() : nullptr;
+  const MerkleAppend a = merkle_append_args(old_size, n, oldw.data(), leafw.data(), nodew.data(),
+                                            roots ? rootsw.data() : nullptr, audit_paths ? pathsw.data() : nullptr);
   for (uint64_t i = 0; i < n; i++) merkle_append_leaf(a, i);
   if (roots) memcpy(roots, rootsw.data(), 32 * n);
   if (audit_paths && entries) memcpy(audit_paths, pathsw.data(), 32 * entries);
@@ -760,20 +754,9 @@ int hc_merkle_verify_inclusion(const uint8_t* leaves, const uint64_t* leaf_off, 
   memcpy(rootw.data(), roots, 32 * n);
   if (entries) memcpy(proofw.data(), proofs + 32 * pbase, 32 * entries);
   std::vector<uint8_t> st(n);
-  MerkleVerifyInclusion a;
-  a.n = n;
-  a.leaves = leaves ? lv : nullptr;
-  a.leaf_off = leaves ? loff.data() : nullptr;
-  a.leaf_base = lbase;
-  a.leaf_hashes = leaves ? nullptr : lhw.data();
-  a.leaf_index = idx.data();
-  a.tree_size = size.data();
-  a.roots = rootw.data();
-  a.proofs = proofw.data();
-  a.proof_off = poff.data();
-  a.proof_base = pbase;
-  a.status = st.data();
-  a.computed = computed ? compw.data() : nullptr;
+  const MerkleVerifyInclusion a = merkle_verify_inclusion_args(
+      n, leaves ? lv : nullptr, leaves ? loff.data() : nullptr, lbase, leaves ? nullptr : lhw.data(), idx.data(),
+      size.data(), rootw.data(), proofw.data(), poff.data(), pbase, st.data(), computed ? compw.data() : nullptr);
   for (uint64_t i = 0; i < n; i++) {
     if (leaves)
       merkle_verify_inclusion_lane<true>(a, i);
@@ -799,17 +782,9 @@ int hc_merkle_verify_consistency(const uint64_t* old_size, const uint64_t* new_s
   memcpy(neww.data(), new_roots, 32 * n);
   if (entries) memcpy(proofw.data(), proofs + 32 * pbase, 32 * entries);
   std::vector<uint8_t> st(n);
-  MerkleVerifyConsistency a;
-  a.n = n;
-  a.old_size = os.data();
-  a.new_size = ns.data();
-  a.old_roots = oldw.data();
-  a.new_roots = neww.data();
-  a.proofs = proofw.data();
-  a.proof_off = poff.data();
-  a.proof_base = pbase;
-  a.status = st.data();
-  a.computed = computed ? compw.data() : nullptr;
+  const MerkleVerifyConsistency a =
+      merkle_verify_consistency_args(n, os.data(), ns.data(), oldw.data(), neww.data(), proofw.data(), poff.data(), pbase,
+                                     st.data(), computed ? compw.data() : nullptr);
   for (uint64_t i = 0; i < n; i++) merkle_verify_consistency_lane(a, i);
   memcpy(status, st.data(), n);
   if (computed) memcpy(computed, compw.data(), 64 * n);

@@ -1,9 +1,12 @@
 // edv_hostplan.h -- the arithmetic of the host paths (edv_runtime.hip): the
 // packed layout of a batch, the single-copy test, slices and sub-batches of a
-// shard, how far buffers grow and what a trim keeps.  Plain C++, no HIP types:
-// libedv_hostcheck.so and tools/ubsan_hostplan.cpp check what the library runs.
+// shard, how far buffers grow and what a trim keeps, the Merkle buffers' sizes.
+// Plain C++, no HIP types: libedv_hostcheck.so and tools/ubsan_hostplan.cpp
+// check what the library runs.
 #pragma once
 #include <stdint.h>
+#include <array>
+#include "edv_merkle.h"
 
 namespace edv {
 
@@ -94,6 +97,64 @@ inline TrimLimits trim_limits(uint64_t keep, uint64_t chunk) {
   return {chunk_capacity(k < chunk ? k : chunk, chunk), 64 * k, 32 * k, k, 32 * k, msgs,
           8 * (k + k / (chunk / 2 ? chunk / 2 : 1) + 2), 8 * (k + 1), packed, blob,
           pinned_capacity(blob), pinned_capacity(k), pinned_capacity(32 * k)};
+}
+
+// ---- the Merkle buffers of a context (edv_runtime.hip: MerkleBufs).  mk_*: the
+// extension and the batched append.  mk_roots (the tile roots the passes hand
+// on) and mk_fleafh / mk_fnodeh (the hashes the per-leaf fold reads) are scratch
+// of every stream; the others are the host form's staging: leaf bytes, offsets,
+// old entries | new entries | root, leaf and node hashes, per-leaf roots, packed
+// paths.  mv_*: the host verify forms' staging: leaf bytes or hashes, every
+// 64-bit array in turn, given roots, proof entries, computed roots | statuses.
+enum MerkleBuf {
+  mk_roots, mk_leaves, mk_off, mk_hashes, mk_leafh, mk_nodeh, mk_fleafh, mk_fnodeh, mk_aroots, mk_paths,
+  mv_leaves, mv_words, mv_roots, mv_proofs, mv_out, kMerkleBufs
+};
+using MerkleSizes = std::array<uint64_t, kMerkleBufs>;  // bytes, by MerkleBuf
+constexpr uint64_t kMerkleHashesBytes = 32 * (2 * kMerkleMaxHashes + 2);  // mk_hashes: old entries | new entries | root
+// What one extend or append of n leaves (mbytes of them) onto old_size needs of
+// each (0: not touched); want_*: the outputs asked for.  The per-leaf fold reads
+// the leaf and node hashes, so with roots or paths wanted they are kept anyway:
+// staged (host form), in the fold scratch (device form without a buffer for them).
+inline MerkleSizes merkle_extend_needs(uint64_t old_size, uint64_t n, uint64_t mbytes, bool host_form, bool want_leaf,
+                                       bool want_node, bool want_roots, bool want_paths) {
+  const uint64_t nodes = merkle_node_count(old_size + n) - merkle_node_count(old_size);
+  const bool per_leaf = n != 0 && (want_roots || want_paths);
+  MerkleSizes s = {};
+  s[mk_roots] = 32 * merkle_scratch_hashes(old_size, old_size + n);
+  if (host_form) {
+    s[mk_leaves] = mbytes + 64;
+    s[mk_off] = 8 * (n + 1);
+    s[mk_hashes] = kMerkleHashesBytes;
+    s[mk_leafh] = want_leaf || per_leaf ? 32 * n : 0;
+    s[mk_nodeh] = want_node || per_leaf ? 32 * nodes : 0;
+    s[mk_aroots] = want_roots ? 32 * n : 0;
+    s[mk_paths] = want_paths ? 32 * merkle_path_entries(old_size, n) : 0;
+  } else {
+    s[mk_fleafh] = per_leaf && !want_leaf ? 32 * n : 0;
+    s[mk_fnodeh] = per_leaf && !want_node ? 32 * nodes : 0;
+  }
+  return s;
+}
+// ... and one host verify call of n proofs of `entries` entries in all; lbytes:
+// the leaves' bytes (inclusion by leaf hash: 32 n).  mv_proofs is never empty.
+inline MerkleSizes merkle_verify_needs(bool inclusion, uint64_t n, uint64_t lbytes, uint64_t entries, bool want_computed) {
+  const uint64_t rbytes = inclusion ? 32 * n : 64 * n;  // one root per proof, or two
+  MerkleSizes s = {};
+  s[mv_leaves] = inclusion ? lbytes + kReadSlack : 0;
+  s[mv_words] = 8 * (4 * n + 2);
+  s[mv_roots] = rbytes;
+  s[mv_proofs] = entries ? 32 * entries : 32;
+  s[mv_out] = (want_computed ? rbytes : 0) + n;
+  return s;
+}
+// What edv_trim lets each keep (t: trim_limits of `keep`): what extending any tree by `keep` leaves of kTrimMsgBytes
+// (paths of at most kMerkleMaxHashes entries) or verifying as many proofs of at most 64 entries can need (mv_out: 64
+// computed bytes and the status, rounded up to 16).
+inline MerkleSizes merkle_trim_limits(uint64_t keep, const TrimLimits& t) {
+  const uint64_t k = keep, h = 32 * k, msgs = k ? t.msgs : 0;
+  return {k ? 32 * (k / (kMerkleT - 1) + 16) : 0, msgs, t.slot_off, k ? kMerkleHashesBytes : 0, h, h, h, h, h,  // MerkleBuf's order
+          h * kMerkleMaxHashes, msgs, k ? 8 * (4 * k + 2) : 0, 64 * k, 64 * h, 80 * k};
 }
 
 }  // namespace edv

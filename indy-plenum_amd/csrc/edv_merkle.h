@@ -21,10 +21,11 @@
 // of height h0 = p kMerkleLogT (leaves in pass 0, the roots of the previous
 // pass's complete tiles after it); a tile is kMerkleT consecutive item indices
 // aligned to kMerkleT, reduced level by level in a pair of buffers (LDS on the
-// device).  Everything here is __host__ __device__: the kernels
+// device).  What a lane runs is __host__ __device__: the kernels
 // (edv_merkle.hip) and the CPU harness (edv_hostcheck.cpp, hc_merkle_extend)
-// are loops over these functions, so the straddling-tile and multi-pass logic
-// is tested without a GPU.
+// are loops over these functions under one host-side pass schedule and
+// argument builders (merkle_for_each_pass, merkle_*_args), so the
+// straddling-tile and multi-pass logic is tested without a GPU.
 //
 // Hashes in memory are their 32 bytes (read and written as little-endian
 // words); in the level buffers they are the eight big-endian state words.
@@ -286,6 +287,33 @@ EDV_HD void merkle_level(const MerklePass& a, uint64_t tile, int hl, uint32_t j,
   if (hl == kMerkleLogT && a.roots_out) merkle_store_hash(a.roots_out + 8 * (k - merkle_block_lo(a.old_size, h)), H);
 }
 
+// A call's passes (host side): what every pass of it shares (hashes at any
+// pointer type), and the schedule: run_pass(a) once per pass that runs, lowest
+// first, with a.h0, a.in and a.roots_out set.  A pass that another follows
+// writes its tiles' roots to the scratch at roots_base (merkle_scratch_hashes
+// entries in all) behind those of the passes before it.  Returns the first
+// nonzero result of run_pass (an int or an error code), or zero.
+inline MerklePass merkle_pass_args(uint64_t old_size, uint64_t new_size, const void* old_hashes, void* leaf_out,
+                                   void* node_out, void* new_hashes) {
+  using H = uint32_t*;
+  return {old_size, new_size, 0, static_cast<const uint32_t*>(old_hashes), nullptr, H(leaf_out), H(node_out),
+          H(new_hashes), nullptr};
+}
+template <class F>
+inline auto merkle_for_each_pass(uint64_t old_size, uint64_t new_size, uint32_t* roots_base, MerklePass& a, F run_pass) {
+  a.in = nullptr;
+  for (int h0 = 0; merkle_pass_runs(old_size, new_size, h0); h0 += kMerkleLogT) {
+    const uint64_t next_items =
+        merkle_pass_runs(old_size, new_size, h0 + kMerkleLogT) ? merkle_pass_items(old_size, new_size, h0 + kMerkleLogT) : 0;
+    a.h0 = h0;
+    a.roots_out = next_items ? roots_base : nullptr;
+    if (const auto rc = run_pass(a)) return rc;
+    a.in = roots_base;
+    roots_base += 8 * next_items;
+  }
+  return decltype(run_pass(a))();
+}
+
 // Finish: the entries of the new tree's hashes that the old tree already had
 // (same index in both), then the root.
 EDV_HD void merkle_finish(uint64_t old_size, uint64_t new_size, const uint32_t* old_hashes, uint32_t* new_hashes,
@@ -331,6 +359,13 @@ EDV_HD uint64_t merkle_popc_prefix(uint64_t x) {
     p += ((x >> (b + 1)) << b) + (rem > half ? rem - half : 0);
   }
   return p;
+}
+// the append kernel's arguments from the call's, field by field (host side; hashes at any pointer type)
+inline MerkleAppend merkle_append_args(uint64_t old_size, uint64_t n, const void* old_hashes, const void* leaf_hashes,
+                                       const void* node_hashes, void* roots, void* paths) {
+  using H = const uint32_t*;
+  return {old_size, n, merkle_popc_prefix(old_size), H(old_hashes), H(leaf_hashes), H(node_hashes),
+          static_cast<uint32_t*>(roots), static_cast<uint32_t*>(paths)};
 }
 // audit-path entries of the first n appends to a tree of old_size leaves
 // (leaf i's path has popcount(old_size + i) entries)
@@ -526,6 +561,15 @@ struct MerkleVerifyInclusion {
   uint8_t* status;
   uint32_t* computed;           // 8 words per proof, or null
 };
+// ... from the call's arguments (host side; hashes at any pointer type): leaves or leaf_hashes, the other null
+inline MerkleVerifyInclusion merkle_verify_inclusion_args(
+    uint64_t n, const uint8_t* leaves, const uint64_t* leaf_off, uint64_t leaf_base, const void* leaf_hashes,
+    const uint64_t* leaf_index, const uint64_t* tree_size, const void* roots, const void* proofs,
+    const uint64_t* proof_off, uint64_t proof_base, uint8_t* status, void* computed) {
+  using H = const uint32_t*;
+  return {n, leaves, leaf_off, leaf_base, H(leaf_hashes), leaf_index, tree_size, H(roots), H(proofs), proof_off,
+          proof_base, status, static_cast<uint32_t*>(computed)};
+}
 // Lane i < a.n.  A lane out of range hashes no leaf.
 template <bool kLeaves>
 EDV_HD void merkle_verify_inclusion_lane(const MerkleVerifyInclusion& a, uint64_t i) {
@@ -565,6 +609,13 @@ struct MerkleVerifyConsistency {
   uint8_t* status;
   uint32_t* computed;  // 16 words per proof (old, then new), or null
 };
+inline MerkleVerifyConsistency merkle_verify_consistency_args(
+    uint64_t n, const uint64_t* old_size, const uint64_t* new_size, const void* old_roots, const void* new_roots,
+    const void* proofs, const uint64_t* proof_off, uint64_t proof_base, uint8_t* status, void* computed) {
+  using H = const uint32_t*;
+  return {n, old_size, new_size, H(old_roots), H(new_roots), H(proofs), proof_off, proof_base, status,
+          static_cast<uint32_t*>(computed)};
+}
 EDV_HD void merkle_verify_consistency_lane(const MerkleVerifyConsistency& a, uint64_t i) {
   const uint64_t p0 = a.proof_off[i], p1 = a.proof_off[i + 1];
   uint32_t ro[8], rn[8], oldr[8], newr[8];

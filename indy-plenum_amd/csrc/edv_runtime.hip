@@ -156,6 +156,41 @@ struct ChunkBufs {
   }
 };
 
+// The Merkle buffers of a context (edv_hostplan.h names and sizes them), none
+// allocated before the call that needs it.  `done` (mk_done) is recorded after
+// the last kernel that used the scratch, on whatever stream; the next user and
+// whoever grows it wait for it (as st_done).  The staging is a host form's under mu.
+struct MerkleBufs {
+  DevBuf b[kMerkleBufs];
+  hipEvent_t done = nullptr;  // created by the first extend (launch_merkle)
+  // the buffer as T*; with `need`: null where the call does not touch it
+  template <class T = uint8_t>
+  T* at(MerkleBuf i) const { return static_cast<T*>(b[i].p); }
+  uint8_t* at(MerkleBuf i, const MerkleSizes& need) const { return need[i] ? at(i) : nullptr; }
+  uint64_t bytes() const {
+    uint64_t t = 0;
+    for (const DevBuf& x : b) t += x.cap;
+    return t;
+  }
+  void trim(const MerkleSizes& limit) {  // the caller guarantees what DevBuf::release asks
+    for (int i = 0; i < kMerkleBufs; i++)
+      if (b[i].cap > limit[i]) b[i].release();
+  }
+  // Grows what is smaller than the call needs.  What grew before a failure stays.
+  int ensure(const MerkleSizes& need) {
+    bool idle = !done;  // the scratch has no queued user (left)
+    for (int i = 0; i < kMerkleBufs; i++) {
+      if (need[i] <= b[i].cap) continue;
+      if (!idle && (i == mk_roots || i == mk_fleafh || i == mk_fnodeh)) {
+        HIPOK(hipEventSynchronize(done), "merkle scratch sync");
+        idle = true;
+      }
+      if (b[i].ensure(need[i])) return EDV_E_OOM;
+    }
+    return 0;
+  }
+};
+
 struct DevCtx {
   std::mutex mu;
   bool ready = false;
@@ -232,30 +267,7 @@ struct DevCtx {
   hipEvent_t perm_done[2] = {nullptr, nullptr};  // split prep: state set b's bucket permutation is written
   bool pending[2] = {false, false};
   int next = 0;
-  // Merkle-tree extension (edv_merkle_extend[_dev]): nothing of it exists until
-  // the first call.  mk_roots: the tile roots the passes hand on (scratch);
-  // mk_done: recorded after the last kernel that used it, on whatever stream,
-  // and waited for by the next user (as st_done for the verify scratch).  The
-  // other buffers are the host form's staging, its alone while it holds mu.
-  DevBuf mk_roots, mk_leaves, mk_off, mk_hashes, mk_leafh, mk_nodeh;
-  // batched append (edv_merkle_append_batch[_dev]): mk_fleafh / mk_fnodeh hold
-  // the leaf and node hashes the fold reads when the device form's caller did
-  // not ask for them (scratch, ordered by mk_done like mk_roots; the host form
-  // uses its own staging mk_leafh / mk_nodeh); mk_aroots / mk_paths are
-  // the host form's staging of the per-leaf roots and the packed audit paths
-  DevBuf mk_fleafh, mk_fnodeh, mk_aroots, mk_paths;
-  hipEvent_t mk_done = nullptr;
-  // proof verification (edv_merkle_verify_inclusion / _consistency): the host
-  // forms' staging, theirs alone while they hold mu (the device forms use no
-  // context memory).  mv_leaves: leaf bytes or leaf hashes; mv_words: every
-  // 64-bit input array, one after another; mv_roots: the given roots;
-  // mv_proofs: the packed entries; mv_out: computed roots, then the statuses.
-  DevBuf mv_leaves, mv_words, mv_roots, mv_proofs, mv_out;
-  uint64_t mk_bytes() const {
-    return mk_roots.cap + mk_leaves.cap + mk_off.cap + mk_hashes.cap + mk_leafh.cap + mk_nodeh.cap +
-           mk_fleafh.cap + mk_fnodeh.cap + mk_aroots.cap + mk_paths.cap + mv_leaves.cap + mv_words.cap +
-           mv_roots.cap + mv_proofs.cap + mv_out.cap;
-  }
+  MerkleBufs mk;                   // the Merkle extension, batched append and proof verification
 #ifdef EDV_MEASUREMENT_API
   int64_t inject_fail = -1;        // edv_test_fail_async (libedv_measure.so only)
 #endif
@@ -396,7 +408,7 @@ void for_each_event(DevCtx& c, F f) {
   for (hipEvent_t* e : {&c.part_copied, &c.part_prepped, &c.st_done}) f(*e, false);
   for (auto* set : {&c.prep_done, &c.main_done, &c.perm_done})
     for (hipEvent_t& e : *set) f(e, true);
-  for (hipEvent_t* e : {&c.inputs_ready, &c.mk_done}) f(*e, true);
+  for (hipEvent_t* e : {&c.inputs_ready, &c.mk.done}) f(*e, true);
 }
 
 // Idempotent: a failure part-way leaves what was created in place and the next
@@ -748,7 +760,7 @@ int drain(DevCtx& c) {
   });
   HIPOK(e, "stream sync");
   HIPOK(hipEventSynchronize(c.st_done), "scratch sync");
-  if (c.mk_done) HIPOK(hipEventSynchronize(c.mk_done), "merkle scratch sync");
+  if (c.mk.done) HIPOK(hipEventSynchronize(c.mk.done), "merkle scratch sync");
   if (c.pipe_ready) c.pending[0] = c.pending[1] = false;
   return 0;
 }
@@ -1292,109 +1304,65 @@ int run_digest_shard(DevCtx& c, const uint8_t* msgs, const uint64_t* off, uint64
 }
 
 // ---- Merkle-tree extension (edv_merkle.h).  Extends (old_size, d_old) by the
-// n leaves at d_leaves / d_off on stream s: one pass per kMerkleLogT heights
-// while a pass has a block to build, then the finish.  d_leafh / d_nodeh may be null.
-// The tile roots go through c.mk_roots, grown here after its queued users are
-// done; launches on different streams are ordered on it by c.mk_done.  Caller
-// holds c.mu.
+// n leaves at d_leaves / d_off on stream s: the passes (merkle_for_each_pass),
+// then the finish.  d_leafh / d_nodeh may be null.  The tile roots go through
+// mk_roots; launches on different streams are ordered on it by c.mk.done.
 // d_aroots / d_paths (either may be null): the per-leaf roots and packed audit
-// paths of the batched append, by one more kernel after the finish.  It reads
-// the call's leaf and node hashes, so where d_leafh / d_nodeh is null they go
-// to c.mk_fleafh / c.mk_fnodeh, scratch under the same event.
+// paths of the batched append, by one more kernel after the finish.  Where it
+// reads leaf or node hashes that d_leafh / d_nodeh do not take, they go to
+// mk_fleafh / mk_fnodeh, scratch under the same event.  Caller holds c.mu.
 int launch_merkle(DevCtx& c, uint64_t old_size, const uint8_t* d_old, const uint8_t* d_leaves, const uint64_t* d_off,
                   uint64_t leaf_base, uint64_t n, uint8_t* d_leafh, uint8_t* d_nodeh, uint8_t* d_new, uint8_t* d_root,
                   hipStream_t s, uint8_t* d_aroots = nullptr, uint8_t* d_paths = nullptr) {
+  MerkleBufs& m = c.mk;
   const uint64_t new_size = old_size + n;
-  if (!c.mk_done) HIPOK(hipEventCreateWithFlags(&c.mk_done, hipEventDisableTiming), "event");
-  const bool per_leaf = n != 0 && (d_aroots || d_paths);
-  const uint64_t nodes = merkle_node_count(new_size) - merkle_node_count(old_size);
-  const uint64_t need = 32 * merkle_scratch_hashes(old_size, new_size);
-  const uint64_t need_leafh = per_leaf && !d_leafh ? 32 * n : 0;
-  const uint64_t need_nodeh = per_leaf && !d_nodeh ? 32 * nodes : 0;
-  if (need > c.mk_roots.cap || need_leafh > c.mk_fleafh.cap || need_nodeh > c.mk_fnodeh.cap) {
-    HIPOK(hipEventSynchronize(c.mk_done), "merkle scratch sync");
-    if (c.mk_roots.ensure(need) || c.mk_fleafh.ensure(need_leafh) || c.mk_fnodeh.ensure(need_nodeh)) return EDV_E_OOM;
-  }
-  const bool scratch = need || need_leafh || need_nodeh;
-  if (scratch) HIPOK(hipStreamWaitEvent(s, c.mk_done, 0), "wait merkle scratch");
-  if (need_leafh) d_leafh = static_cast<uint8_t*>(c.mk_fleafh.p);
-  if (need_nodeh) d_nodeh = static_cast<uint8_t*>(c.mk_fnodeh.p);
-  MerklePass a;
-  a.old_size = old_size;
-  a.new_size = new_size;
-  a.old_hashes = reinterpret_cast<const uint32_t*>(d_old);
-  a.leaf_out = reinterpret_cast<uint32_t*>(d_leafh);
-  a.node_out = reinterpret_cast<uint32_t*>(d_nodeh);
-  a.new_hashes = reinterpret_cast<uint32_t*>(d_new);
-  a.in = nullptr;
-  uint32_t* roots = static_cast<uint32_t*>(c.mk_roots.p);
-  for (int h0 = 0; merkle_pass_runs(old_size, new_size, h0); h0 += kMerkleLogT) {
-    const uint64_t next_items =
-        merkle_pass_runs(old_size, new_size, h0 + kMerkleLogT) ? merkle_pass_items(old_size, new_size, h0 + kMerkleLogT) : 0;
-    a.h0 = h0;
-    a.roots_out = next_items ? roots : nullptr;
-    HIPOK(launch_merkle_pass_kernel(s, a, d_leaves, d_off, leaf_base), "merkle pass launch");
-    a.in = roots;
-    roots += 8 * next_items;
-  }
+  if (!m.done) HIPOK(hipEventCreateWithFlags(&m.done, hipEventDisableTiming), "event");
+  const MerkleSizes need = merkle_extend_needs(old_size, n, 0, false, d_leafh, d_nodeh, d_aroots, d_paths);
+  if (const int err = m.ensure(need)) return err;
+  const bool scratch = need[mk_roots] || need[mk_fleafh] || need[mk_fnodeh];
+  if (scratch) HIPOK(hipStreamWaitEvent(s, m.done, 0), "wait merkle scratch");
+  if (need[mk_fleafh]) d_leafh = m.at(mk_fleafh);
+  if (need[mk_fnodeh]) d_nodeh = m.at(mk_fnodeh);
+  MerklePass a = merkle_pass_args(old_size, new_size, d_old, d_leafh, d_nodeh, d_new);
+  HIPOK(merkle_for_each_pass(old_size, new_size, m.at<uint32_t>(mk_roots), a,
+                             [&](const MerklePass& p) { return launch_merkle_pass_kernel(s, p, d_leaves, d_off, leaf_base); }),
+        "merkle pass launch");
   HIPOK(launch_merkle_finish_kernel(s, old_size, new_size, a.old_hashes, a.new_hashes,
                                     reinterpret_cast<uint32_t*>(d_root)),
         "merkle finish launch");
-  if (per_leaf) {
-    MerkleAppend ap;
-    ap.old_size = old_size;
-    ap.n = n;
-    ap.path_base = merkle_popc_prefix(old_size);
-    ap.old_hashes = a.old_hashes;
-    ap.leaf_hashes = a.leaf_out;
-    ap.node_hashes = a.node_out;
-    ap.roots = reinterpret_cast<uint32_t*>(d_aroots);
-    ap.paths = reinterpret_cast<uint32_t*>(d_paths);
-    HIPOK(launch_merkle_append_kernel(s, ap), "merkle append launch");
-  }
-  if (scratch) HIPOK(hipEventRecord(c.mk_done, s), "record merkle scratch");
+  if (n && (d_aroots || d_paths))
+    HIPOK(launch_merkle_append_kernel(s, merkle_append_args(old_size, n, d_old, d_leafh, d_nodeh, d_aroots, d_paths)),
+          "merkle append launch");
+  if (scratch) HIPOK(hipEventRecord(m.done, s), "record merkle scratch");
   return 0;
 }
 
-// The host form: staged like run_digest_shard, in buffers of its own; copies
-// back only the outputs asked for (roots / audit_paths: the batched append's,
-// null from edv_merkle_extend).  The per-leaf fold reads the leaf and node
-// hashes on the device, so with roots or audit_paths wanted they are staged in
-// mk_leafh / mk_nodeh whether the caller asked for them or not, and only the
-// copy back is skipped (mk_fleafh / mk_fnodeh are the device form's alone).
-// Caller holds c.mu.
+// The host form: staged like run_digest_shard, in buffers of its own
+// (merkle_extend_needs); copies back only the outputs asked for (roots /
+// audit_paths: the batched append's, null from edv_merkle_extend).  Caller
+// holds c.mu.
 int run_merkle_host(DevCtx& c, uint64_t old_size, const uint8_t* old_hashes, const uint8_t* leaves, const uint64_t* off,
                     uint64_t n, uint8_t* leaf_hashes, uint8_t* node_hashes, uint8_t* new_hashes, uint8_t* root,
                     uint8_t* roots = nullptr, uint8_t* audit_paths = nullptr) {
-  const uint64_t new_size = old_size + n;
+  MerkleBufs& m = c.mk;
+  const uint64_t new_size = old_size + n, nodes = merkle_node_count(new_size) - merkle_node_count(old_size);
   const uint64_t nold = uint64_t(popc64(old_size)), nnew = uint64_t(popc64(new_size));
-  const uint64_t nodes = merkle_node_count(new_size) - merkle_node_count(old_size);
   const uint64_t mbase = n ? off[0] : 0, mbytes = n ? off[n] - off[0] : 0;
-  const uint64_t pbytes = audit_paths ? 32 * merkle_path_entries(old_size, n) : 0;
-  const bool per_leaf = n != 0 && (roots || audit_paths);
-  // mk_hashes: old entries | new entries | root, 32 bytes each
-  if (c.mk_leaves.ensure(mbytes + 64) || c.mk_off.ensure((n + 1) * 8) ||
-      c.mk_hashes.ensure(32 * (2 * kMerkleMaxHashes + 2)) || ((leaf_hashes || per_leaf) && c.mk_leafh.ensure(32 * n)) ||
-      ((node_hashes || per_leaf) && c.mk_nodeh.ensure(32 * nodes)) || (roots && c.mk_aroots.ensure(32 * n)) ||
-      c.mk_paths.ensure(pbytes))
-    return EDV_E_OOM;
+  const MerkleSizes need = merkle_extend_needs(old_size, n, mbytes, true, leaf_hashes, node_hashes, roots, audit_paths);
+  if (const int err = m.ensure(need)) return err;
   const hipStream_t s = c.stream;
-  uint8_t* d_old = static_cast<uint8_t*>(c.mk_hashes.p);
-  uint8_t* d_new = d_old + 32 * kMerkleMaxHashes;
-  uint8_t* d_root = d_new + 32 * kMerkleMaxHashes;
-  if (mbytes) HIPOK(hipMemcpyAsync(c.mk_leaves.p, leaves + mbase, mbytes, hipMemcpyHostToDevice, s), "h2d leaves");
-  if (n) HIPOK(hipMemcpyAsync(c.mk_off.p, off, (n + 1) * 8, hipMemcpyHostToDevice, s), "h2d leaf_off");
+  uint8_t *d_old = m.at(mk_hashes), *d_new = d_old + 32 * kMerkleMaxHashes, *d_root = d_new + 32 * kMerkleMaxHashes;
+  if (mbytes) HIPOK(hipMemcpyAsync(m.at(mk_leaves), leaves + mbase, mbytes, hipMemcpyHostToDevice, s), "h2d leaves");
+  if (n) HIPOK(hipMemcpyAsync(m.at(mk_off), off, (n + 1) * 8, hipMemcpyHostToDevice, s), "h2d leaf_off");
   if (nold) HIPOK(hipMemcpyAsync(d_old, old_hashes, 32 * nold, hipMemcpyHostToDevice, s), "h2d old hashes");
-  uint8_t* d_leafh = (leaf_hashes || per_leaf) && n ? static_cast<uint8_t*>(c.mk_leafh.p) : nullptr;
-  uint8_t* d_nodeh = (node_hashes || per_leaf) && nodes ? static_cast<uint8_t*>(c.mk_nodeh.p) : nullptr;
-  uint8_t* d_aroots = roots && n ? static_cast<uint8_t*>(c.mk_aroots.p) : nullptr;
-  uint8_t* d_paths = pbytes ? static_cast<uint8_t*>(c.mk_paths.p) : nullptr;
-  int err;
-  if ((err = launch_merkle(c, old_size, d_old, static_cast<uint8_t*>(c.mk_leaves.p), static_cast<uint64_t*>(c.mk_off.p),
-                           mbase, n, d_leafh, d_nodeh, d_new, d_root, s, d_aroots, d_paths)))
+  // null where nothing is to be written: no leaves, no nodes, not asked for and not read by the fold
+  uint8_t *d_leafh = m.at(mk_leafh, need), *d_nodeh = m.at(mk_nodeh, need), *d_aroots = m.at(mk_aroots, need),
+          *d_paths = m.at(mk_paths, need);
+  if (const int err = launch_merkle(c, old_size, d_old, m.at(mk_leaves), m.at<uint64_t>(mk_off), mbase, n, d_leafh,
+                                    d_nodeh, d_new, d_root, s, d_aroots, d_paths))
     return err;
   if (d_aroots) HIPOK(hipMemcpyAsync(roots, d_aroots, 32 * n, hipMemcpyDeviceToHost, s), "d2h roots");
-  if (d_paths) HIPOK(hipMemcpyAsync(audit_paths, d_paths, pbytes, hipMemcpyDeviceToHost, s), "d2h audit paths");
+  if (d_paths) HIPOK(hipMemcpyAsync(audit_paths, d_paths, need[mk_paths], hipMemcpyDeviceToHost, s), "d2h audit paths");
   if (leaf_hashes && d_leafh) HIPOK(hipMemcpyAsync(leaf_hashes, d_leafh, 32 * n, hipMemcpyDeviceToHost, s), "d2h leaf hashes");
   if (node_hashes && d_nodeh) HIPOK(hipMemcpyAsync(node_hashes, d_nodeh, 32 * nodes, hipMemcpyDeviceToHost, s), "d2h node hashes");
   if (nnew) HIPOK(hipMemcpyAsync(new_hashes, d_new, 32 * nnew, hipMemcpyDeviceToHost, s), "d2h new hashes");
@@ -1404,38 +1372,33 @@ int run_merkle_host(DevCtx& c, uint64_t old_size, const uint8_t* old_hashes, con
 }
 
 // ---- proof verification (edv_merkle.h, row f-7).  The host forms: inputs
-// staged in the context's mv_* buffers, one launch on the library stream, the
-// statuses (and the computed roots, if asked for) copied back, synchronous.
-// The 64-bit arrays go into mv_words one after another (each starts on a
-// multiple of 8 bytes); the windows [off[0], off[n]) of the leaf bytes and of
-// the proof entries are what is copied, and off[0] is the kernel's base.
+// staged in the mv_* buffers (merkle_verify_needs), the device forms' launch
+// on the library stream, the statuses (and the computed roots, if asked for)
+// copied back, synchronous.  The windows [off[0], off[n]) of the leaf bytes and
+// of the proof entries are what is copied, and off[0] is the kernel's base.
 // Caller holds c.mu and has checked the arguments.
 struct WordStage {
-  uint64_t* base;
-  uint64_t used = 0;
+  uint64_t* next;  // mv_words, from its start
   hipStream_t s;
-  const uint64_t* put(const uint64_t* src, uint64_t count, hipError_t* e) {
-    uint64_t* d = base + used;
-    used += count;
-    if (*e == hipSuccess) *e = hipMemcpyAsync(d, src, 8 * count, hipMemcpyHostToDevice, s);
-    return d;
+  hipError_t e = hipSuccess;  // the first copy's that failed
+  const uint64_t* put(const uint64_t* src, uint64_t count) {
+    if (e == hipSuccess) e = hipMemcpyAsync(next, src, 8 * count, hipMemcpyHostToDevice, s);
+    next += count;
+    return next - count;
   }
 };
-int stage_proofs(DevCtx& c, const uint8_t* proofs, const uint64_t* proof_off, uint64_t n, const uint32_t** d_proofs) {
-  const uint64_t bytes = 32 * (proof_off[n] - proof_off[0]);
-  if (c.mv_proofs.ensure(bytes ? bytes : 32)) return EDV_E_OOM;
-  if (bytes)
-    HIPOK(hipMemcpyAsync(c.mv_proofs.p, proofs + 32 * proof_off[0], bytes, hipMemcpyHostToDevice, c.stream),
+int stage_proofs(DevCtx& c, const uint8_t* proofs, const uint64_t* proof_off, uint64_t n) {
+  if (const uint64_t bytes = 32 * (proof_off[n] - proof_off[0]))
+    HIPOK(hipMemcpyAsync(c.mk.at(mv_proofs), proofs + 32 * proof_off[0], bytes, hipMemcpyHostToDevice, c.stream),
           "h2d proofs");
-  *d_proofs = static_cast<const uint32_t*>(c.mv_proofs.p);
   return 0;
 }
 // launch(d_status, d_computed) runs the kernel; cbytes: computed bytes per proof
 template <class Launch>
 int run_proofs_out(DevCtx& c, uint64_t n, uint64_t cbytes, uint8_t* status, uint8_t* computed, Launch launch) {
-  uint8_t* d_comp = computed ? static_cast<uint8_t*>(c.mv_out.p) : nullptr;
-  uint8_t* d_status = static_cast<uint8_t*>(c.mv_out.p) + (computed ? cbytes * n : 0);
-  HIPOK(launch(d_status, reinterpret_cast<uint32_t*>(d_comp)), "merkle verify launch");
+  uint8_t* d_comp = computed ? c.mk.at(mv_out) : nullptr;
+  uint8_t* d_status = c.mk.at(mv_out) + (computed ? cbytes * n : 0);
+  HIPOK(launch(d_status, d_comp), "merkle verify launch");
   HIPOK(hipMemcpyAsync(status, d_status, n, hipMemcpyDeviceToHost, c.stream), "d2h proof status");
   if (computed) HIPOK(hipMemcpyAsync(computed, d_comp, cbytes * n, hipMemcpyDeviceToHost, c.stream), "d2h computed roots");
   HIPOK(hipStreamSynchronize(c.stream), "stream sync");
@@ -1446,64 +1409,44 @@ int run_verify_inclusion_host(DevCtx& c, const uint8_t* leaves, const uint64_t* 
                               const uint64_t* leaf_index, const uint64_t* tree_size, const uint8_t* roots,
                               const uint8_t* proofs, const uint64_t* proof_off, uint64_t n, uint8_t* status,
                               uint8_t* computed) {
+  MerkleBufs& m = c.mk;
   const hipStream_t s = c.stream;
   const uint64_t lbytes = leaves ? leaf_off[n] - leaf_off[0] : 32 * n;
-  if (c.mv_leaves.ensure(lbytes + kReadSlack) || c.mv_words.ensure(8 * (4 * n + 2)) || c.mv_roots.ensure(32 * n) ||
-      c.mv_out.ensure((computed ? 32 * n : 0) + n))
-    return EDV_E_OOM;
-  MerkleVerifyInclusion a;
-  int err;
-  if ((err = stage_proofs(c, proofs, proof_off, n, &a.proofs))) return err;
+  if (const int err = m.ensure(merkle_verify_needs(true, n, lbytes, proof_off[n] - proof_off[0], computed))) return err;
+  if (const int err = stage_proofs(c, proofs, proof_off, n)) return err;
   if (lbytes)
-    HIPOK(hipMemcpyAsync(c.mv_leaves.p, leaves ? leaves + leaf_off[0] : leaf_hashes, lbytes, hipMemcpyHostToDevice, s),
+    HIPOK(hipMemcpyAsync(m.at(mv_leaves), leaves ? leaves + leaf_off[0] : leaf_hashes, lbytes, hipMemcpyHostToDevice, s),
           "h2d leaves");
-  HIPOK(hipMemcpyAsync(c.mv_roots.p, roots, 32 * n, hipMemcpyHostToDevice, s), "h2d roots");
-  WordStage w{static_cast<uint64_t*>(c.mv_words.p), 0, s};
-  hipError_t e = hipSuccess;
-  a.n = n;
-  a.leaves = leaves ? static_cast<const uint8_t*>(c.mv_leaves.p) : nullptr;
-  a.leaf_off = leaves ? w.put(leaf_off, n + 1, &e) : nullptr;
-  a.leaf_base = leaves ? leaf_off[0] : 0;
-  a.leaf_hashes = leaves ? nullptr : static_cast<const uint32_t*>(c.mv_leaves.p);
-  a.leaf_index = w.put(leaf_index, n, &e);
-  a.tree_size = w.put(tree_size, n, &e);
-  a.proof_off = w.put(proof_off, n + 1, &e);
-  a.proof_base = proof_off[0];
-  a.roots = static_cast<const uint32_t*>(c.mv_roots.p);
-  HIPOK(e, "h2d proof words");
-  return run_proofs_out(c, n, 32, status, computed, [&](uint8_t* d_status, uint32_t* d_comp) {
-    a.status = d_status;
-    a.computed = d_comp;
-    return launch_merkle_verify_inclusion_kernel(s, a);
+  HIPOK(hipMemcpyAsync(m.at(mv_roots), roots, 32 * n, hipMemcpyHostToDevice, s), "h2d roots");
+  WordStage w{m.at<uint64_t>(mv_words), s};
+  const uint64_t* d_leaf_off = leaves ? w.put(leaf_off, n + 1) : nullptr;
+  const uint64_t *d_index = w.put(leaf_index, n), *d_size = w.put(tree_size, n), *d_poff = w.put(proof_off, n + 1);
+  HIPOK(w.e, "h2d proof words");
+  return run_proofs_out(c, n, 32, status, computed, [&](uint8_t* d_status, uint8_t* d_comp) {
+    return launch_merkle_verify_inclusion_kernel(
+        s, merkle_verify_inclusion_args(n, leaves ? m.at(mv_leaves) : nullptr, d_leaf_off, leaves ? leaf_off[0] : 0,
+                                        leaves ? nullptr : m.at(mv_leaves), d_index, d_size, m.at(mv_roots),
+                                        m.at(mv_proofs), d_poff, proof_off[0], d_status, d_comp));
   });
 }
 
 int run_verify_consistency_host(DevCtx& c, const uint64_t* old_size, const uint64_t* new_size, const uint8_t* old_roots,
                                 const uint8_t* new_roots, const uint8_t* proofs, const uint64_t* proof_off, uint64_t n,
                                 uint8_t* status, uint8_t* computed) {
+  MerkleBufs& m = c.mk;
   const hipStream_t s = c.stream;
-  if (c.mv_words.ensure(8 * (4 * n + 2)) || c.mv_roots.ensure(64 * n) || c.mv_out.ensure((computed ? 64 * n : 0) + n))
-    return EDV_E_OOM;
-  MerkleVerifyConsistency a;
-  int err;
-  if ((err = stage_proofs(c, proofs, proof_off, n, &a.proofs))) return err;
-  uint8_t* d_roots = static_cast<uint8_t*>(c.mv_roots.p);
+  if (const int err = m.ensure(merkle_verify_needs(false, n, 0, proof_off[n] - proof_off[0], computed))) return err;
+  if (const int err = stage_proofs(c, proofs, proof_off, n)) return err;
+  uint8_t* d_roots = m.at(mv_roots);
   HIPOK(hipMemcpyAsync(d_roots, old_roots, 32 * n, hipMemcpyHostToDevice, s), "h2d old roots");
   HIPOK(hipMemcpyAsync(d_roots + 32 * n, new_roots, 32 * n, hipMemcpyHostToDevice, s), "h2d new roots");
-  WordStage w{static_cast<uint64_t*>(c.mv_words.p), 0, s};
-  hipError_t e = hipSuccess;
-  a.n = n;
-  a.old_size = w.put(old_size, n, &e);
-  a.new_size = w.put(new_size, n, &e);
-  a.proof_off = w.put(proof_off, n + 1, &e);
-  a.proof_base = proof_off[0];
-  a.old_roots = reinterpret_cast<const uint32_t*>(d_roots);
-  a.new_roots = reinterpret_cast<const uint32_t*>(d_roots + 32 * n);
-  HIPOK(e, "h2d proof words");
-  return run_proofs_out(c, n, 64, status, computed, [&](uint8_t* d_status, uint32_t* d_comp) {
-    a.status = d_status;
-    a.computed = d_comp;
-    return launch_merkle_verify_consistency_kernel(s, a);
+  WordStage w{m.at<uint64_t>(mv_words), s};
+  const uint64_t *d_old = w.put(old_size, n), *d_new = w.put(new_size, n), *d_poff = w.put(proof_off, n + 1);
+  HIPOK(w.e, "h2d proof words");
+  return run_proofs_out(c, n, 64, status, computed, [&](uint8_t* d_status, uint8_t* d_comp) {
+    return launch_merkle_verify_consistency_kernel(
+        s, merkle_verify_consistency_args(n, d_old, d_new, d_roots, d_roots + 32 * n, m.at(mv_proofs), d_poff,
+                                          proof_off[0], d_status, d_comp));
   });
 }
 
@@ -1853,23 +1796,7 @@ void trim_buffers(DevCtx& c, uint64_t keep) {
   dev(c.qstage, t.stage);
   dev(c.acc_host, t.acc_host);
   for (int q = 0; q < kQ; q++) dev(c.stage[q], t.stage);
-  // the Merkle buffers: what extending any tree by k leaves of kTrimMsgBytes can need
-  dev(c.mk_roots, k ? 32 * (k / (kMerkleT - 1) + 16) : 0);
-  dev(c.mk_leaves, k ? t.msgs : 0);
-  dev(c.mk_off, t.slot_off);
-  dev(c.mk_hashes, k ? 32 * (2 * kMerkleMaxHashes + 2) : 0);
-  dev(c.mk_leafh, 32 * k);
-  dev(c.mk_nodeh, 32 * k);
-  dev(c.mk_fleafh, 32 * k);
-  dev(c.mk_fnodeh, 32 * k);
-  dev(c.mk_aroots, 32 * k);
-  dev(c.mk_paths, 32 * kMerkleMaxHashes * k);  // a path is at most kMerkleMaxHashes entries
-  // proof verification: k proofs of at most 64 entries, leaves of kTrimMsgBytes
-  dev(c.mv_leaves, k ? t.msgs : 0);
-  dev(c.mv_words, k ? 8 * (4 * k + 2) : 0);
-  dev(c.mv_roots, 64 * k);
-  dev(c.mv_proofs, 32 * 64 * k);
-  dev(c.mv_out, 80 * k);  // 64 computed bytes (consistency) and the status, rounded up to 16
+  c.mk.trim(merkle_trim_limits(keep, t));
   for (auto& a : c.as) {
     set(a.cb);
     dev(a.sigs, t.sigs);
@@ -2112,7 +2039,7 @@ int edv_context_memory(int device, uint64_t out[7]) {
   std::lock_guard<std::mutex> lk(c->mu);
   if (!c->ready) return 0;
   out[1] = shared_tables_bytes(c->phys);
-  out[2] = c->st.bytes() + c->mk_bytes();
+  out[2] = c->st.bytes() + c->mk.bytes();
   for (const auto& a : c->as)
     out[3] += a.sigs.cap + a.pks.cap + a.msgs.cap + a.off.cap + a.acc.cap + a.dig.cap + a.cb.bytes() + a.qtab.cap;
   out[4] = c->pst[0].bytes() + c->pst[1].bytes();
@@ -2299,17 +2226,25 @@ int edv_merkle_extend(uint64_t old_size, const uint8_t* old_hashes, const uint8_
                                  nullptr, nullptr, device);
 }
 
+// What both forms of an append check first: the sizes and the pointers every
+// call needs; d: "d_" for the device form's names in the messages.
+static int check_append_args(uint64_t old_size, uint64_t n, const void* old_hashes, const void* new_hashes,
+                             const void* root, const std::string& d) {
+  if (n > EDV_MERKLE_MAX_LEAVES) return set_err(EDV_E_ARG, "merkle: more than EDV_MERKLE_MAX_LEAVES leaves");
+  if (old_size > kMerkleMaxSize || old_size + n > kMerkleMaxSize) return set_err(EDV_E_ARG, "merkle: tree size above 2^62");
+  if (old_size && !old_hashes) return set_err(EDV_E_ARG, ("merkle: null " + d + "old_hashes").c_str());
+  if (!new_hashes || !root) return set_err(EDV_E_ARG, ("merkle: null " + d + "new_hashes / " + d + "root").c_str());
+  return 0;
+}
+
 int edv_merkle_append_batch(uint64_t old_size, const uint8_t* old_hashes, const uint8_t* leaves,
                             const uint64_t* leaf_off, uint64_t n, uint8_t* leaf_hashes, uint8_t* node_hashes,
                             uint8_t* new_hashes, uint8_t* root, uint8_t* roots, uint8_t* audit_paths, int device) {
   g_err.clear();
-  if (n > EDV_MERKLE_MAX_LEAVES) return set_err(EDV_E_ARG, "merkle: more than EDV_MERKLE_MAX_LEAVES leaves");
-  if (old_size > kMerkleMaxSize || old_size + n > kMerkleMaxSize) return set_err(EDV_E_ARG, "merkle: tree size above 2^62");
-  if (old_size && !old_hashes) return set_err(EDV_E_ARG, "merkle: null old_hashes");
-  if (!new_hashes || !root) return set_err(EDV_E_ARG, "merkle: null new_hashes / root");
+  int err;
+  if ((err = check_append_args(old_size, n, old_hashes, new_hashes, root, ""))) return err;
   if (n) {
     if (!leaf_off) return set_err(EDV_E_ARG, "merkle: null leaf_off");
-    int err;
     if ((err = check_offsets(leaf_off, n))) return err;
     if (!leaves && leaf_off[n] != leaf_off[0]) return set_err(EDV_E_ARG, "merkle: null leaves");
   }
@@ -2340,13 +2275,11 @@ int edv_merkle_append_batch_dev(uint64_t old_size, const uint8_t* d_old_hashes, 
                                 uint8_t* d_node_hashes, uint8_t* d_new_hashes, uint8_t* d_root, uint8_t* d_roots,
                                 uint8_t* d_audit_paths, int device, void* stream) {
   g_err.clear();
+  int err;
+  if ((err = check_append_args(old_size, n, d_old_hashes, d_new_hashes, d_root, "d_"))) return err;
+  if (n && (!d_leaves || !d_leaf_off)) return set_err(EDV_E_ARG, "merkle: null d_leaves / d_leaf_off");
   // before anything reaches the GPU: the kernels read the offsets as 64-bit
   // words and read and store every hash as two 16-byte vectors
-  if (n > EDV_MERKLE_MAX_LEAVES) return set_err(EDV_E_ARG, "merkle: more than EDV_MERKLE_MAX_LEAVES leaves");
-  if (old_size > kMerkleMaxSize || old_size + n > kMerkleMaxSize) return set_err(EDV_E_ARG, "merkle: tree size above 2^62");
-  if (old_size && !d_old_hashes) return set_err(EDV_E_ARG, "merkle: null d_old_hashes");
-  if (!d_new_hashes || !d_root) return set_err(EDV_E_ARG, "merkle: null d_new_hashes / d_root");
-  if (n && (!d_leaves || !d_leaf_off)) return set_err(EDV_E_ARG, "merkle: null d_leaves / d_leaf_off");
   if (reinterpret_cast<uintptr_t>(d_leaf_off) & 7) return set_err(EDV_E_ARG, "merkle: d_leaf_off must be 8-byte aligned");
   for (const uint8_t* p : {d_old_hashes, static_cast<const uint8_t*>(d_leaf_hashes),
                            static_cast<const uint8_t*>(d_node_hashes), static_cast<const uint8_t*>(d_new_hashes),
@@ -2356,7 +2289,6 @@ int edv_merkle_append_batch_dev(uint64_t old_size, const uint8_t* d_old_hashes, 
   CtxLock cl(device);
   if (cl.err) return cl.err;
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : cl.c->stream;
-  int err;
   if ((err = launch_merkle(*cl.c, old_size, d_old_hashes, d_leaves, d_leaf_off, leaf_base, n, d_leaf_hashes,
                            d_node_hashes, d_new_hashes, d_root, s, d_roots, d_audit_paths)))
     return err;
@@ -2427,21 +2359,10 @@ int edv_merkle_verify_inclusion_dev(const uint8_t* d_leaves, const uint64_t* d_l
   CtxLock cl(device);
   if (cl.err) return cl.err;
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : cl.c->stream;
-  MerkleVerifyInclusion a;
-  a.n = n;
-  a.leaves = d_leaves;
-  a.leaf_off = d_leaf_off;
-  a.leaf_base = leaf_base;
-  a.leaf_hashes = reinterpret_cast<const uint32_t*>(d_leaf_hashes);
-  a.leaf_index = d_leaf_index;
-  a.tree_size = d_tree_size;
-  a.roots = reinterpret_cast<const uint32_t*>(d_roots);
-  a.proofs = reinterpret_cast<const uint32_t*>(d_proofs);
-  a.proof_off = d_proof_off;
-  a.proof_base = proof_base;
-  a.status = d_status;
-  a.computed = reinterpret_cast<uint32_t*>(d_computed);
-  HIPOK(launch_merkle_verify_inclusion_kernel(s, a), "merkle verify launch");
+  HIPOK(launch_merkle_verify_inclusion_kernel(
+            s, merkle_verify_inclusion_args(n, d_leaves, d_leaf_off, leaf_base, d_leaf_hashes, d_leaf_index, d_tree_size,
+                                            d_roots, d_proofs, d_proof_off, proof_base, d_status, d_computed)),
+        "merkle verify launch");
   if (!stream) HIPOK(hipStreamSynchronize(s), "stream sync");
   return 0;
 }
@@ -2479,18 +2400,10 @@ int edv_merkle_verify_consistency_dev(const uint64_t* d_old_size, const uint64_t
   CtxLock cl(device);
   if (cl.err) return cl.err;
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : cl.c->stream;
-  MerkleVerifyConsistency a;
-  a.n = n;
-  a.old_size = d_old_size;
-  a.new_size = d_new_size;
-  a.old_roots = reinterpret_cast<const uint32_t*>(d_old_roots);
-  a.new_roots = reinterpret_cast<const uint32_t*>(d_new_roots);
-  a.proofs = reinterpret_cast<const uint32_t*>(d_proofs);
-  a.proof_off = d_proof_off;
-  a.proof_base = proof_base;
-  a.status = d_status;
-  a.computed = reinterpret_cast<uint32_t*>(d_computed);
-  HIPOK(launch_merkle_verify_consistency_kernel(s, a), "merkle verify launch");
+  HIPOK(launch_merkle_verify_consistency_kernel(
+            s, merkle_verify_consistency_args(n, d_old_size, d_new_size, d_old_roots, d_new_roots, d_proofs, d_proof_off,
+                                              proof_base, d_status, d_computed)),
+        "merkle verify launch");
   if (!stream) HIPOK(hipStreamSynchronize(s), "stream sync");
   return 0;
 }

@@ -485,7 +485,7 @@ def latency_kernel(n, quad):
     return None
 
 
-# -- the fifteen Merkle buffers of a context (DevCtx::mk_bytes), as the runtime sizes and trims them
+# -- the fifteen Merkle buffers of a context (MerkleBufs::bytes), as the runtime sizes and trims them
 K_MERKLE_LOG_T, K_MERKLE_MAX_HASHES, K_READ_SLACK, K_TRIM_MSG_BYTES = 8, 63, 64, 4096
 MERKLE_BUFFERS = ("mk_roots", "mk_leaves", "mk_off", "mk_hashes", "mk_leafh", "mk_nodeh", "mk_fleafh", "mk_fnodeh",
                   "mk_aroots", "mk_paths", "mv_leaves", "mv_words", "mv_roots", "mv_proofs", "mv_out")

@@ -1,9 +1,10 @@
 """The host paths' arithmetic (csrc/edv_hostplan.h) through the CPU build
 libedv_hostcheck.so: the packed layout of a batch, the single-copy test, the
 capacity rules, the field path's slices, the sub-batch split and the trim
-limits, each against a plain Python restatement of its rule written here, and
-the same sweeps under UBSan + ASan as a stand-alone program
-(tools/ubsan_hostplan.cpp)."""
+limits, each against a plain Python restatement of its rule written here, the
+sizes and trim limits of the fifteen Merkle buffers against the model of
+tests/sequence_cases.py, and the same sweeps under UBSan + ASan as a
+stand-alone program (tools/ubsan_hostplan.cpp)."""
 import ctypes
 import os
 import shutil
@@ -180,6 +181,132 @@ def test_trim_limits(hc):
                 assert got[0] == hc.hc_chunk_capacity(min(keep, chunk), chunk)
                 assert got[10] == hc.hc_pinned_capacity(got[9]) and got[11] == hc.hc_pinned_capacity(keep)
                 assert got[8] >= 104 * keep + 8 and got[9] >= outs(hc.hc_packed_layout, 5, keep, keep * 4096)[1][4]
+
+
+# ------------------------------------------------------ the Merkle buffers
+# The plan (merkle_extend_needs, merkle_verify_needs, merkle_trim_limits) against the model the device sequence
+# tests hold edv_context_memory to (sequence_cases.merkle_needs / merkle_trim_limits, written from the arguments
+# alone), entry by entry over the fifteen buffers.
+MERKLE_OLD = [0, 1, 255, 256, 257, 2**20 + 12345, 2**62 - 300]
+MERKLE_N = [0, 1, 255, 256, 257, 300]
+MERKLE_KEEP = [0, 1, 254, 255, 256, 400, 2**20]
+
+
+def model_row(sc, needs):
+    want = dict.fromkeys(sc.MERKLE_BUFFERS, 0)
+    for name, size in needs:
+        assert want[name] == 0, "the model names %s twice" % name
+        want[name] = size
+    return [want[name] for name in sc.MERKLE_BUFFERS]
+
+
+def plan_row(hc, sc, op, chain_step=None):
+    """the plan's row for a Merkle operation of the sequence tests, from the operation's own parameters and inputs"""
+    k = op.kind
+    if k in ("verify_incl_host", "verify_cons_host"):
+        c = sc.proof_case("incl" if "incl" in k else "cons", op.n, op.seed)
+        incl = k == "verify_incl_host"
+        lbytes = (32 * op.n if op.by_hash else c["lbytes"]) if incl else 0
+        return outs(hc.hc_merkle_verify_needs, 15, int(incl), op.n, lbytes, c["entries"], int(bool(op.computed)))[1]
+    if k == "chain_append":
+        old, mbytes = chain_step["start"], 0
+        flags = {"roots": True, "paths": True, "leaf": op.keep_hashes, "node": op.keep_hashes}
+    elif k.startswith("append"):
+        c = sc.append_inputs(op.old, op.n)
+        old, mbytes, flags = c["old"], c["mbytes"], {f: op.p[f] for f in sc.APPEND_FLAGS}
+    else:
+        c = sc.merkle_inputs(op.old, op.n)
+        old, mbytes = c["old"], c["mbytes"]
+        flags = {"roots": False, "paths": False, "leaf": op.get("leaf", True), "node": op.get("node", True)}
+    host = k in ("merkle_host", "append_host")
+    return outs(hc.hc_merkle_extend_needs, 15, old, op.n, mbytes, int(host), int(bool(flags["leaf"])),
+                int(bool(flags["node"])), int(bool(flags["roots"])), int(bool(flags["paths"])))[1]
+
+
+@pytest.fixture(scope="module")
+def mhc(hc):
+    hc.hc_merkle_extend_needs.argtypes = [U64, U64, U64] + [ctypes.c_int] * 5 + [ctypes.c_void_p]
+    hc.hc_merkle_verify_needs.argtypes = [ctypes.c_int, U64, U64, U64, ctypes.c_int, ctypes.c_void_p]
+    hc.hc_merkle_trim_limits.argtypes = [U64, ctypes.c_void_p]
+    return hc
+
+
+MERKLE_LISTS = ("merkle_staging", "merkle_fold_streams", "ledger_chain", "release_in_the_middle", "random_merkle_110",
+                "random_merkle_214")
+
+
+@pytest.mark.parametrize("name", MERKLE_LISTS)
+def test_merkle_needs_of_the_sequence_lists(mhc, monkeypatch, name):
+    import sequence_cases as sc
+    ops, devices, _seed = sc.sequence(name)
+    seen, model = [], sc.merkle_needs
+
+    def recording(op, chain_step=None):
+        needs = model(op, chain_step)
+        seen.append((op, chain_step, needs))
+        return needs
+    monkeypatch.setattr(sc, "merkle_needs", recording)
+    trace = sc.trace_of(ops, devices)
+    merkle_ops = [op for op in ops if op.kind in ("merkle_host", "merkle_device", "append_host", "append_device",
+                                                  "chain_append", "verify_incl_host", "verify_cons_host")]
+    assert [s[0] for s in seen] == merkle_ops and (merkle_ops or name == "release_in_the_middle"), name
+    for op, chain_step, needs in seen:
+        assert plan_row(mhc, sc, op, chain_step) == model_row(sc, needs), (name, op)
+    for t in trace:
+        if t["kind"] == "trim":
+            k = t["op"].keep
+            assert outs(mhc.hc_merkle_trim_limits, 15, k)[1] == model_row(sc, sc.merkle_trim_limits(k).items()), (name, k)
+
+
+def test_merkle_extend_needs_sweep(mhc, monkeypatch):
+    import merkle_append_cases as ac
+    import merkle_cases as mc
+    import sequence_cases as sc
+
+    def inputs(old, n):  # the sizes alone: `old` is the tree size itself here, no leaves are made
+        return {"old": old, "n": n, "nodes": mc.node_span(old, n), "mbytes": 700 * n + 3, "entries": ac.path_entries(old, n)}
+    monkeypatch.setattr(sc, "append_inputs", inputs)
+    for old in MERKLE_OLD:
+        for n in MERKLE_N:
+            assert old + n <= 2**62
+            for bits in range(16):
+                flags = {f: bool(bits >> i & 1) for i, f in enumerate(sc.APPEND_FLAGS)}
+                for host in (1, 0):
+                    op = sc.Op("append_host" if host else "append_device", old=old, n=n, **flags)
+                    got = plan_row(mhc, sc, op)
+                    assert got == model_row(sc, sc.merkle_needs(op)), (old, n, flags, host)
+                    assert all(g == 0 for g, b in zip(got, sc.MERKLE_BUFFERS) if b.startswith("mv_"))
+
+
+def test_merkle_verify_needs_sweep(mhc, monkeypatch):
+    import sequence_cases as sc
+    for n in MERKLE_N[1:] + [4097]:
+        for entries in (0, 1, 64 * n):
+            monkeypatch.setattr(sc, "proof_case", lambda kind, n_, seed: {"entries": entries, "lbytes": 300 * n_ + 1})
+            for kind in ("verify_incl_host", "verify_cons_host"):
+                for computed in (False, True):
+                    for by_hash in ((False, True) if "incl" in kind else (False,)):
+                        op = sc.Op(kind, n=n, seed=0, computed=computed, by_hash=by_hash)
+                        got = plan_row(mhc, sc, op)
+                        assert got == model_row(sc, sc.merkle_needs(op)), (n, entries, kind, computed, by_hash)
+                        assert got[sc.MERKLE_BUFFERS.index("mv_proofs")] >= 32, "mv_proofs is never asked for empty"
+
+
+def test_merkle_trim_limits(mhc):
+    import sequence_cases as sc
+    for keep in MERKLE_KEEP + list(sc.TRIMS):
+        got = outs(mhc.hc_merkle_trim_limits, 15, keep)[1]
+        assert got == model_row(sc, sc.merkle_trim_limits(keep).items()), keep
+        if keep:  # what an extend or a verify of `keep` leaves of 4,096 bytes needs survives the trim
+            old = 2**20 + 12345
+            for host in (1, 0):
+                need = outs(mhc.hc_merkle_extend_needs, 15, old, keep, 4096 * keep, host, 0, 0, 1, 1)[1]
+                # ... but for the node hashes, limited to 32 keep: n leaves make up to n + popcount(old) - 1 nodes
+                slack = [32 * bin(old).count("1") if "nodeh" in b else 0 for b in sc.MERKLE_BUFFERS]
+                assert all(n <= g + s for n, g, s in zip(need, got, slack)), (keep, host)
+            for incl in (1, 0):
+                need = outs(mhc.hc_merkle_verify_needs, 15, incl, keep, 4096 * keep, 64 * keep, 1)[1]
+                assert all(n <= g for n, g in zip(need, got)), (keep, incl)
 
 
 # ---------------------------------------------------- the sanitizer program

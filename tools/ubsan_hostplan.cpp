@@ -5,8 +5,9 @@
 // The header's functions index rb[] and shift and divide by what they are
 // given: the sanitizers abort the run on a write past rb[kSlices], a division
 // by zero or an overflowing shift, and the properties a caller relies on (the
-// slices and sub-batches partition the shard, nothing exceeds its scratch) are
-// checked here.  Prints "ok <cases> <checksum>" over every result.
+// slices and sub-batches partition the shard, nothing exceeds its scratch, the
+// Merkle buffers hold what a call of either form reads and writes, for tree
+// sizes up to 2^62) are checked here.  Prints "ok <cases> <checksum>" over every result.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -75,6 +76,57 @@ int main() {
       eat(sp.nsub ^ cap ^ t.stage ^ t.off);
       cases++;
     }
+  }
+  // the Merkle buffers' sizes: tree sizes up to old + n = 2^62, every combination of the outputs, both forms
+  for (uint64_t old : {uint64_t(0), uint64_t(1), uint64_t(255), uint64_t(256), uint64_t(257), (uint64_t(1) << 20) + 12345,
+                       kMerkleMaxSize - 300})
+    for (uint64_t n : {0, 1, 255, 256, 257, 300})
+      for (int bits = 0; bits < 32; bits++) {
+        const bool host = bits & 16, leaf = bits & 1, node = bits & 2, roots = bits & 4, paths = bits & 8;
+        const MerkleSizes s = merkle_extend_needs(old, n, 700 * n + 3, host, leaf, node, roots, paths);
+        const uint64_t nodes = merkle_node_count(old + n) - merkle_node_count(old);
+        must(s[mk_roots] == 32 * merkle_scratch_hashes(old, old + n) && s[mk_roots] <= 32 * (n / (kMerkleT - 1) + 16),
+             "merkle: tile-root scratch", old, n);
+        must(host ? s[mk_fleafh] == 0 && s[mk_fnodeh] == 0 && s[mk_off] == 8 * (n + 1) && s[mk_paths] <= 32 * 63 * n
+                  : s[mk_leaves] == 0 && s[mk_leafh] == 0 && s[mk_nodeh] == 0 && s[mk_aroots] == 0 && s[mk_paths] == 0,
+             "merkle: a form touches the other's buffers", old, n);
+        // with per-leaf outputs the fold finds the leaf and node hashes somewhere: the caller's buffer or one of these
+        if (n && (roots || paths))
+          must((host ? s[mk_leafh] : leaf ? 32 * n : s[mk_fleafh]) == 32 * n &&
+                   (host ? s[mk_nodeh] : node ? 32 * nodes : s[mk_fnodeh]) == 32 * nodes,
+               "merkle: the fold's hashes", old, n);
+        for (int i = mv_leaves; i < kMerkleBufs; i++) must(s[i] == 0, "merkle: an extend touches a verify buffer", old, n);
+        for (uint64_t v : s) eat(v);
+        cases++;
+      }
+  for (uint64_t n : {1, 255, 256, 257, 300, 4097})
+    for (uint64_t entries : {uint64_t(0), uint64_t(1), 64 * n})
+      for (int bits = 0; bits < 4; bits++) {
+        const MerkleSizes s = merkle_verify_needs(bits & 1, n, 300 * n + 1, entries, bits & 2);
+        must(s[mv_proofs] >= 32 && s[mv_proofs] >= 32 * entries && s[mv_out] >= n && s[mv_words] >= 8 * (3 * n + 1 + (bits & 1) * (n + 1)),
+             "merkle verify: staging", n, entries);
+        for (int i = 0; i < mv_leaves; i++) must(s[i] == 0, "merkle verify: touches an extend buffer", n, entries);
+        for (uint64_t v : s) eat(v);
+        cases++;
+      }
+  for (uint64_t keep : {uint64_t(0), uint64_t(1), uint64_t(254), uint64_t(255), uint64_t(256), uint64_t(400), uint64_t(1) << 20}) {
+    const MerkleSizes t = merkle_trim_limits(keep, trim_limits(keep, uint64_t(1) << 18));
+    // what extending a tree by `keep` leaves of kTrimMsgBytes, or verifying as many proofs of 64 entries, needs survives
+    // (but for the node hashes, limited to 32 keep: n leaves make up to n + popcount(old) - 1 nodes)
+    const uint64_t old = (uint64_t(1) << 20) + 12345;
+    for (int host = 0; host < 2; host++) {
+      const MerkleSizes s = merkle_extend_needs(old, keep, kTrimMsgBytes * keep, host, false, false, true, true);
+      for (int i = 0; i < kMerkleBufs; i++) {
+        const uint64_t slack = i == mk_nodeh || i == mk_fnodeh ? 32 * uint64_t(popc64(old)) : 0;
+        must(!keep ? t[i] == 0 : s[i] <= t[i] + slack, "merkle trim: an extend of keep leaves", keep, i);
+      }
+    }
+    for (int incl = 0; incl < 2; incl++) {
+      const MerkleSizes s = merkle_verify_needs(incl, keep, kTrimMsgBytes * keep, 64 * keep, true);
+      for (int i = 0; i < kMerkleBufs; i++) must(!keep || s[i] <= t[i], "merkle trim: a verify of keep proofs", keep, i);
+    }
+    for (uint64_t v : t) eat(v);
+    cases++;
   }
   printf("ok %llu %016llx\n", (unsigned long long)cases, (unsigned long long)sum);
   return 0;
