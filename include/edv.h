@@ -338,6 +338,84 @@ int edv_merkle_verify_consistency_dev(const uint64_t *d_old_size, const uint64_t
                                       uint8_t *d_status, uint8_t *d_computed, int device, void *stream);
 
 /*
+ * Batched proof generation (row f-8): what the reference's CompactMerkleTree
+ * reads out of its hash store one proof at a time (ledger/compact_merkle_tree.py
+ * merkle_tree_hash / inclusion_proof / consistency_proof) for every reply
+ * (ledger/ledger.py:197-206 merkleInfo, called by plenum/server/node.py:3024-3034
+ * getReplyFromLedger) and in catch-up (plenum/common/ledger_manager.py:448-452,
+ * :995-998, :1117-1120), for n proofs in one call, one lane per proof, from a
+ * hash store in device memory.
+ *   leaf_store  the leaf hashes in order, store_leaves x 32 bytes
+ *   node_store  the interior nodes in the order the appends create them (what
+ *               edv_merkle_extend writes as node_hashes, tree after tree):
+ *               (store_leaves - popcount(store_leaves)) x 32 bytes
+ *   leaf_index / tree_size   inclusion: PATH(leaf_index, D[0:tree_size])
+ *   first / second           consistency: PROOF(first, D[0:second])
+ *   proof_off   n + 1 offsets IN ENTRIES: proof i is written to entries
+ *               [proof_off[i], proof_off[i + 1]) of `proofs`, lowest level
+ *               first: the layout edv_merkle_verify_* reads
+ *   status      n bytes: EDV_PROOF_RANGE (inclusion: leaf_index >= tree_size or
+ *               tree_size > store_leaves; consistency: first == 0, first >
+ *               second or second > store_leaves), else EDV_PROOF_SPACE (the
+ *               slot's length is not the proof's), else EDV_PROOF_OK, and only
+ *               then is the slot written.  first == second is OK and empty
+ *   roots       NULL, or n x 32 bytes: MTH(D[0:tree_size])
+ *   leaf_hashes_out   NULL, or n x 32 bytes: the stored hash of the leaf; with
+ *               it one call yields every input of edv_merkle_verify_inclusion
+ *   old_roots / new_roots   NULL, or n x 32 bytes: MTH(D[0:first]), MTH(D[0:second])
+ *               These outputs hold zeros where the status is not OK.
+ * A proof's entries are stored hashes, copied, but at most one, which the fold
+ * of the tree head yields on its way: a lane hashes popcount(tree_size) - 1
+ * nodes with or without roots wanted (fewer without), and popcount(first) - 1
+ * more for old_roots.  Audit paths have at most 62 entries, consistency proofs
+ * 63.  No store position at or past the counts is read, nothing outside a
+ * proof's own slot is written.
+ * The offset helpers touch no device: they fill the n + 1 packed offsets from
+ * 0 that fit the proofs exactly (a pair that gets RANGE takes no entries).
+ * EDV_E_ARG: a NULL pointer.
+ * n = 0 is valid and writes nothing.  EDV_E_ARG with nothing launched or
+ * written: n above EDV_MERKLE_MAX_LEAVES; store_leaves above 2^62; with n > 0 a
+ * NULL index array, proof_off, proofs or status; NULL leaf_store with
+ * store_leaves > 0, NULL node_store with store_leaves > 1; host offsets that
+ * decrease.
+ * Device forms: async on `stream` (NULL = library stream, synchronised before
+ * returning), offsets absolute minus proof_base; no context memory, so calls
+ * are ordered by their streams alone.  Alignment as edv_merkle_verify_*_dev:
+ * 64-bit arrays on 8 bytes, hash buffers and both stores on 16, d_status any.
+ * The outputs must not overlap the stores.
+ * Host forms: fill status with EDV_PROOF_UNVERIFIED, synchronous.  THEY COPY
+ * THE STORE TO THE DEVICE ON EVERY CALL: the prefix the largest valid tree size
+ * reads, 64 bytes per leaf of it.  They exist for small stores and for callers
+ * without device memory; a ledger keeps its store on the device and uses the
+ * device forms.  Their staging grows by use, counts in edv_context_memory
+ * out[2], is cut by edv_trim to what keep_batch proofs of 64 entries need (all
+ * of it for 0) and freed by edv_release; only these calls allocate it.
+ */
+#define EDV_PROOF_SPACE 7 /* proof generation only: the slot's length is not the proof's; nothing else written */
+int edv_merkle_inclusion_offsets(const uint64_t *leaf_index, const uint64_t *tree_size, uint64_t n,
+                                 uint64_t store_leaves, uint64_t *proof_off);
+int edv_merkle_consistency_offsets(const uint64_t *first, const uint64_t *second, uint64_t n,
+                                   uint64_t store_leaves, uint64_t *proof_off);
+int edv_merkle_prove_inclusion(const uint8_t *leaf_store, const uint8_t *node_store, uint64_t store_leaves,
+                               const uint64_t *leaf_index, const uint64_t *tree_size,
+                               const uint64_t *proof_off, uint64_t n, uint8_t *proofs,
+                               uint8_t *status, uint8_t *roots, uint8_t *leaf_hashes_out, int device);
+int edv_merkle_prove_consistency(const uint8_t *leaf_store, const uint8_t *node_store, uint64_t store_leaves,
+                                 const uint64_t *first, const uint64_t *second,
+                                 const uint64_t *proof_off, uint64_t n, uint8_t *proofs,
+                                 uint8_t *status, uint8_t *old_roots, uint8_t *new_roots, int device);
+int edv_merkle_prove_inclusion_dev(const uint8_t *d_leaf_store, const uint8_t *d_node_store, uint64_t store_leaves,
+                                   const uint64_t *d_leaf_index, const uint64_t *d_tree_size,
+                                   const uint64_t *d_proof_off, uint64_t proof_base, uint64_t n, uint8_t *d_proofs,
+                                   uint8_t *d_status, uint8_t *d_roots, uint8_t *d_leaf_hashes_out,
+                                   int device, void *stream);
+int edv_merkle_prove_consistency_dev(const uint8_t *d_leaf_store, const uint8_t *d_node_store, uint64_t store_leaves,
+                                     const uint64_t *d_first, const uint64_t *d_second,
+                                     const uint64_t *d_proof_off, uint64_t proof_base, uint64_t n, uint8_t *d_proofs,
+                                     uint8_t *d_status, uint8_t *d_old_roots, uint8_t *d_new_roots,
+                                     int device, void *stream);
+
+/*
  * Pipelined submission of device-resident batches (a continuous stream of
  * client batches, e.g. one per Node prod): enqueues the batch and returns
  * without waiting.  Consecutive submissions alternate between two internal

@@ -547,7 +547,29 @@ void hc_trim_limits(uint64_t keep, uint64_t chunk, uint64_t* out13) {
   memcpy(out13, v, sizeof v);
 }
 // the Merkle buffers' sizes, out: one row of kMerkleBufs = 15 in MerkleBuf's order (no Merkle limit depends on the chunk)
-static void put_sizes(uint64_t* out15, const MerkleSizes& s) { memcpy(out15, s.data(), sizeof s); }
+static void put_sizes(uint64_t* out15, const MerkleSizes& s) { memcpy(out15, s.data(), 8 * kMerkleBufsV7); }
+// ... and whole rows of kMerkleBufs = 20, the prove forms' staging (mp_*, row f-8) after the 15
+void hc_merkle_prove_needs(uint64_t n, uint64_t prefix, uint64_t entries, int want_first, int want_second, uint64_t* out20) {
+  const MerkleSizes s = merkle_prove_needs(n, prefix, entries, want_first, want_second);
+  memcpy(out20, s.data(), sizeof s);
+}
+void hc_merkle_trim_limits_all(uint64_t keep, uint64_t* out20) {
+  const MerkleSizes s = merkle_trim_limits(keep, trim_limits(keep, uint64_t(1) << 18));
+  memcpy(out20, s.data(), sizeof s);
+}
+uint64_t hc_merkle_prove_prefix(int consistency, const uint64_t* a, const uint64_t* b, uint64_t n, uint64_t store_leaves) {
+  return merkle_prove_prefix(consistency, a, b, n, store_leaves);
+}
+void hc_merkle_prove_offsets(int consistency, const uint64_t* a, const uint64_t* b, uint64_t n, uint64_t store_leaves,
+                             uint64_t* proof_off) {
+  merkle_prove_offsets(consistency, a, b, n, store_leaves, proof_off);
+}
+// out: first, second, status, bytes
+void hc_merkle_prove_out(uint64_t n, int want_first, int want_second, uint64_t* out4) {
+  const MerkleProveOut o = merkle_prove_out(n, want_first, want_second);
+  const uint64_t v[4] = {o.first, o.second, o.status, o.bytes};
+  memcpy(out4, v, sizeof v);
+}
 void hc_merkle_extend_needs(uint64_t old_size, uint64_t n, uint64_t mbytes, int host_form, int want_leaf, int want_node,
                             int want_roots, int want_paths, uint64_t* out15) {
   put_sizes(out15, merkle_extend_needs(old_size, n, mbytes, host_form, want_leaf, want_node, want_roots, want_paths));
@@ -789,5 +811,60 @@ int hc_merkle_verify_consistency(const uint64_t* old_size, const uint64_t* new_s
   memcpy(status, st.data(), n);
   if (computed) memcpy(computed, compw.data(), 64 * n);
   return 0;
+}
+
+// ---- proof generation (edv_merkle.h, row f-8)
+// out: kProofSpace, kMerkleMaxProof, kMerkleBufs
+void hc_merkle_prove_consts(int32_t* out) { out[0] = kProofSpace; out[1] = kMerkleMaxProof; out[2] = kMerkleBufs; }
+uint64_t hc_merkle_inclusion_length(uint64_t m, uint64_t n) { return merkle_inclusion_length(m, n); }
+uint64_t hc_merkle_consistency_length(uint64_t first, uint64_t second) { return merkle_consistency_length(first, second); }
+// kind / off: room for kMerkleMaxProof entries; the pair must be in range (m < n, or 1 <= a <= n), n <= 2^62
+int hc_merkle_proof_positions(int consistency, uint64_t a, uint64_t n, uint8_t* kind, uint64_t* off) {
+  if (n == 0 || n > kMerkleMaxSize || (consistency ? (a == 0 || a > n) : a >= n)) return -1;
+  return merkle_proof_positions(consistency, a, n, kind, off);
+}
+// The host C-ABI forms' signatures minus `device`: the kernels' lanes one after
+// another.  The two stores go into heap blocks of exactly the sizes the counts
+// give, the slots [proof_off[0], proof_off[n]) into one of exactly their
+// entries (copied in first, so what no lane writes keeps the caller's bytes),
+// so a lane reading or writing one hash too far is ASan's to see.
+extern "C++" template <class Args, class Lane>
+int hc_prove(const uint8_t* leaf_store, const uint8_t* node_store, uint64_t store_leaves, const uint64_t* a,
+                    const uint64_t* b, const uint64_t* proof_off, uint64_t n, uint8_t* proofs, uint8_t* status,
+                    uint8_t* out1, uint8_t* out2, Args make, Lane lane) {
+  if (n > (uint64_t(1) << 22) || store_leaves > kMerkleMaxSize) return -1;
+  if (n == 0) return 0;
+  if (!a || !b || !proof_off || !proofs || !status || (store_leaves && !leaf_store) || (store_leaves > 1 && !node_store))
+    return -1;
+  if (!hc_offsets_ok(proof_off, n)) return -1;
+  memset(status, kProofUnverified, n);
+  const uint64_t nodes = merkle_node_count(store_leaves), pbase = proof_off[0], entries = proof_off[n] - proof_off[0];
+  std::vector<uint32_t> leafw(8 * store_leaves), nodew(8 * nodes), proofw(8 * entries), o1(out1 ? 8 * n : 0),
+      o2(out2 ? 8 * n : 0);
+  std::vector<uint64_t> av(a, a + n), bv(b, b + n), poff(proof_off, proof_off + n + 1);
+  if (store_leaves) memcpy(leafw.data(), leaf_store, 32 * store_leaves);
+  if (nodes) memcpy(nodew.data(), node_store, 32 * nodes);
+  if (entries) memcpy(proofw.data(), proofs + 32 * pbase, 32 * entries);
+  std::vector<uint8_t> st(n);
+  const auto args = make(leafw.data(), nodew.data(), store_leaves, av.data(), bv.data(), poff.data(), pbase, n,
+                         proofw.data(), st.data(), out1 ? o1.data() : nullptr, out2 ? o2.data() : nullptr);
+  for (uint64_t i = 0; i < n; i++) lane(args, i);
+  if (entries) memcpy(proofs + 32 * pbase, proofw.data(), 32 * entries);
+  memcpy(status, st.data(), n);
+  if (out1) memcpy(out1, o1.data(), 32 * n);
+  if (out2) memcpy(out2, o2.data(), 32 * n);
+  return 0;
+}
+int hc_merkle_prove_inclusion(const uint8_t* leaf_store, const uint8_t* node_store, uint64_t store_leaves,
+                              const uint64_t* leaf_index, const uint64_t* tree_size, const uint64_t* proof_off, uint64_t n,
+                              uint8_t* proofs, uint8_t* status, uint8_t* roots, uint8_t* leaf_hashes_out) {
+  return hc_prove(leaf_store, node_store, store_leaves, leaf_index, tree_size, proof_off, n, proofs, status, roots,
+                  leaf_hashes_out, merkle_prove_inclusion_args, merkle_prove_inclusion_lane);
+}
+int hc_merkle_prove_consistency(const uint8_t* leaf_store, const uint8_t* node_store, uint64_t store_leaves,
+                                const uint64_t* first, const uint64_t* second, const uint64_t* proof_off, uint64_t n,
+                                uint8_t* proofs, uint8_t* status, uint8_t* old_roots, uint8_t* new_roots) {
+  return hc_prove(leaf_store, node_store, store_leaves, first, second, proof_off, n, proofs, status, old_roots, new_roots,
+                  merkle_prove_consistency_args, merkle_prove_consistency_lane);
 }
 }

@@ -106,10 +106,16 @@ inline TrimLimits trim_limits(uint64_t keep, uint64_t chunk) {
 // old entries | new entries | root, leaf and node hashes, per-leaf roots, packed
 // paths.  mv_*: the host verify forms' staging: leaf bytes or hashes, every
 // 64-bit array in turn, given roots, proof entries, computed roots | statuses.
+// mp_*: the host prove forms' staging (row f-8): the prefix of the leaf store
+// and of the node store the call reads, every 64-bit array in turn, the proof
+// entries, roots (consistency: old | new) | leaf hashes | statuses.  The
+// earlier buffers keep their places: kMerkleBufsV7 of them.
 enum MerkleBuf {
   mk_roots, mk_leaves, mk_off, mk_hashes, mk_leafh, mk_nodeh, mk_fleafh, mk_fnodeh, mk_aroots, mk_paths,
-  mv_leaves, mv_words, mv_roots, mv_proofs, mv_out, kMerkleBufs
+  mv_leaves, mv_words, mv_roots, mv_proofs, mv_out,
+  mp_leaves, mp_nodes, mp_words, mp_proofs, mp_out, kMerkleBufs
 };
+constexpr int kMerkleBufsV7 = mp_leaves;
 using MerkleSizes = std::array<uint64_t, kMerkleBufs>;  // bytes, by MerkleBuf
 constexpr uint64_t kMerkleHashesBytes = 32 * (2 * kMerkleMaxHashes + 2);  // mk_hashes: old entries | new entries | root
 // What one extend or append of n leaves (mbytes of them) onto old_size needs of
@@ -150,11 +156,68 @@ inline MerkleSizes merkle_verify_needs(bool inclusion, uint64_t n, uint64_t lbyt
 }
 // What edv_trim lets each keep (t: trim_limits of `keep`): what extending any tree by `keep` leaves of kTrimMsgBytes
 // (paths of at most kMerkleMaxHashes entries) or verifying as many proofs of at most 64 entries can need (mv_out: 64
-// computed bytes and the status, rounded up to 16).
+// computed bytes and the status, rounded up to 16); for the prove forms (mp_*) as many proofs of 64 entries: the
+// entries, as many store hashes of either kind as the lanes can read, two roots, a leaf hash and the status.
 inline MerkleSizes merkle_trim_limits(uint64_t keep, const TrimLimits& t) {
   const uint64_t k = keep, h = 32 * k, msgs = k ? t.msgs : 0;
   return {k ? 32 * (k / (kMerkleT - 1) + 16) : 0, msgs, t.slot_off, k ? kMerkleHashesBytes : 0, h, h, h, h, h,  // MerkleBuf's order
-          h * kMerkleMaxHashes, msgs, k ? 8 * (4 * k + 2) : 0, 64 * k, 64 * h, 80 * k};
+          h * kMerkleMaxHashes, msgs, k ? 8 * (4 * k + 2) : 0, 64 * k, 64 * h, 80 * k,
+          64 * h, 64 * h, k ? 8 * (3 * k + 1) : 0, 64 * h, 112 * k};
+}
+
+// ---- proof generation (row f-8).  What the host forms stage of the store: the
+// prefix the largest valid tree size reads, in leaves (0: every pair is RANGE).
+// size_of_pair: the pair's tree size (tree_size[i] / second[i]) if the pair is
+// in range, else 0.
+inline uint64_t merkle_prove_inclusion_size(uint64_t idx, uint64_t size, uint64_t store_leaves) {
+  return idx < size && size <= store_leaves ? size : 0;
+}
+inline uint64_t merkle_prove_consistency_size(uint64_t first, uint64_t second, uint64_t store_leaves) {
+  return first != 0 && first <= second && second <= store_leaves ? second : 0;
+}
+inline uint64_t merkle_prove_prefix(bool consistency, const uint64_t* a, const uint64_t* b, uint64_t n,
+                                    uint64_t store_leaves) {
+  uint64_t top = 0;
+  for (uint64_t i = 0; i < n; i++) {
+    const uint64_t s = consistency ? merkle_prove_consistency_size(a[i], b[i], store_leaves)
+                                   : merkle_prove_inclusion_size(a[i], b[i], store_leaves);
+    if (s > top) top = s;
+  }
+  return top;
+}
+// The slots a batch needs, packed: n + 1 offsets in entries from 0; a pair that
+// would get RANGE takes none.
+inline void merkle_prove_offsets(bool consistency, const uint64_t* a, const uint64_t* b, uint64_t n,
+                                 uint64_t store_leaves, uint64_t* proof_off) {
+  uint64_t at = 0;
+  for (uint64_t i = 0; i < n; i++) {
+    proof_off[i] = at;
+    if (consistency ? merkle_prove_consistency_size(a[i], b[i], store_leaves) != 0
+                    : merkle_prove_inclusion_size(a[i], b[i], store_leaves) != 0)
+      at += consistency ? merkle_consistency_length(a[i], b[i]) : merkle_inclusion_length(a[i], b[i]);
+  }
+  proof_off[n] = at;
+}
+// Offsets inside mp_out: the first roots, the second (consistency: the new
+// roots; inclusion: the leaf hashes), the statuses.  A part not wanted is left
+// out, so the statuses follow whatever is there.
+struct MerkleProveOut {
+  uint64_t first, second, status, bytes;  // byte offsets; first / second are valid where wanted
+};
+inline MerkleProveOut merkle_prove_out(uint64_t n, bool want_first, bool want_second) {
+  const uint64_t f = 0, s = want_first ? 32 * n : 0, st = s + (want_second ? 32 * n : 0);
+  return {f, s, st, st + n};
+}
+// What one host prove call of n proofs over `entries` slot entries needs:
+// `prefix` leaves of the store (merkle_prove_prefix).  mp_proofs is never empty.
+inline MerkleSizes merkle_prove_needs(uint64_t n, uint64_t prefix, uint64_t entries, bool want_first, bool want_second) {
+  MerkleSizes s = {};
+  s[mp_leaves] = prefix ? 32 * prefix : 32;
+  s[mp_nodes] = prefix > 1 ? 32 * merkle_node_count(prefix) : 32;
+  s[mp_words] = 8 * (3 * n + 1);
+  s[mp_proofs] = entries ? 32 * entries : 32;
+  s[mp_out] = merkle_prove_out(n, want_first, want_second).bytes;
+  return s;
 }
 
 }  // namespace edv

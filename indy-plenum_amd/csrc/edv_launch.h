@@ -54,5 +54,11 @@ struct MerkleVerifyInclusion;
 struct MerkleVerifyConsistency;
 hipError_t launch_merkle_verify_inclusion_kernel(hipStream_t s, const MerkleVerifyInclusion& a);
 hipError_t launch_merkle_verify_consistency_kernel(hipStream_t s, const MerkleVerifyConsistency& a);
+// proof generation from a stored tree (MerkleProveInclusion /
+// MerkleProveConsistency: edv_merkle.h), one lane per proof; no launch for n = 0
+struct MerkleProveInclusion;
+struct MerkleProveConsistency;
+hipError_t launch_merkle_prove_inclusion_kernel(hipStream_t s, const MerkleProveInclusion& a);
+hipError_t launch_merkle_prove_consistency_kernel(hipStream_t s, const MerkleProveConsistency& a);
 
 }  // namespace edv

@@ -2,7 +2,9 @@
 // (SURVEY.md section 8f row f-5), and what each of the appends returns: the
 // root after it and its audit path (row f-6), and the checking of such proofs:
 // audit paths and consistency proofs, a batch at a time (row f-7, at the end of
-// this file; ledger/merkle_verifier.py MerkleVerifier).
+// this file; ledger/merkle_verifier.py MerkleVerifier), and the making of them
+// from the stored hashes (row f-8, after it; CompactMerkleTree.inclusion_proof
+// / consistency_proof / merkle_tree_hash(0, n)).
 //
 // Replaces, per batch of transactions:
 //   ledger/ledger.py:145-148              Ledger._addToTree (one append per txn)
@@ -632,6 +634,269 @@ EDV_HD void merkle_verify_consistency_lane(const MerkleVerifyConsistency& a, uin
     }
     merkle_store_hash(a.computed + 16 * i, oldr);
     merkle_store_hash(a.computed + 16 * i + 8, newr);
+  }
+}
+
+// ---- proof generation from a stored tree (row f-8: what CompactMerkleTree.
+// inclusion_proof / consistency_proof / merkle_tree_hash(0, n) read out of the
+// hash store, one lane per proof).  Written from RFC 6962 sections 2.1.1 and
+// 2.1.2: the walks above run backwards.  The store is the appends': leaf hash
+// k (0-based) at byte 32 k of the leaf store, block k of height h >= 1 at byte
+// 32 (merkle_store_pos(h, k) - 1) of the node store.  Every proof entry is
+// MTH(D[a:b]) of a sibling on the way up; all of them are complete aligned
+// subtrees, which are stored, but at most one: a right sibling cut off by the
+// tree's end, [a, n) with a = (n >> h) << h, whose leaves are the subtrees of
+// the set bits of n below h.  Folding the root of the n leaves in merkle_fold's
+// order (lowest set bit first), the accumulator is that entry at the moment the
+// bits below h are consumed, so it costs no hash beyond the root's.  (With one
+// set bit below h the range is itself a complete subtree and is read.)
+constexpr uint8_t kProofSpace = 7;  // EDV_PROOF_SPACE: the slot's length is not the proof's
+constexpr int kMerkleMaxProof = 63; // entries: an audit path has at most 62, a consistency proof 63 (sizes <= 2^62)
+constexpr uint8_t kEntryLeaf = 0, kEntryNode = 1, kEntryFold = 2;  // where an entry comes from
+
+// The walk of one proof over a tree of n leaves, 1 <= n <= 2^62: entries come
+// out lowest level first.  seed: a consistency proof's first entry, the subtree
+// (h, node) that ends at `first`, when first is no power of two.
+struct MerkleProofWalk {
+  uint64_t node, last, n;
+  int h;
+  bool seed;
+};
+EDV_HD MerkleProofWalk merkle_inclusion_walk(uint64_t m, uint64_t n) { return {m, n - 1, n, 0, false}; }
+// 1 <= first <= second; first == second: no entries
+EDV_HD MerkleProofWalk merkle_consistency_walk(uint64_t first, uint64_t second) {
+  if (first == second) return {0, 0, second, 0, false};
+  uint64_t node = first - 1, last = second - 1;
+  int h = 0;
+  while (node & 1) {
+    node >>= 1;
+    last >>= 1;
+    h++;
+  }
+  return {node, last, second, h, node != 0};
+}
+// store offset in bytes of the complete subtree of height h, block k
+EDV_HD uint8_t merkle_subtree_pos(int h, uint64_t k, uint64_t* off) {
+  if (h == 0) {
+    *off = 32 * k;
+    return kEntryLeaf;
+  }
+  *off = 32 * (merkle_store_pos(h, k) - 1);
+  return kEntryNode;
+}
+// The next entry: false when the walk is over.  kEntryLeaf / kEntryNode: *off
+// is its byte offset into that store; kEntryFold: *off is the height h of the
+// cut-off sibling, the fold's accumulator once the set bits of n below h are in.
+EDV_HD bool merkle_walk_next(MerkleProofWalk& w, uint8_t* kind, uint64_t* off) {
+  if (w.seed) {
+    w.seed = false;
+    *kind = merkle_subtree_pos(w.h, w.node, off);
+    return true;
+  }
+  while (w.last > 0) {
+    const uint64_t node = w.node, last = w.last;
+    const int h = w.h;
+    w.node >>= 1;
+    w.last >>= 1;
+    w.h++;
+    if (node & 1) {
+      *kind = merkle_subtree_pos(h, node - 1, off);
+      return true;
+    }
+    if (node < last) {
+      const uint64_t k = node + 1, start = k << h, rem = w.n - start;  // (k + 1) << h <= n + 2^h: no overflow
+      if (((k + 1) << h) <= w.n) {
+        *kind = merkle_subtree_pos(h, k, off);
+      } else if ((rem & (rem - 1)) == 0) {  // one subtree of height ctz(rem), aligned: start is a multiple of 2^h
+        const int j = __builtin_ctzll(rem);
+        *kind = merkle_subtree_pos(j, start >> j, off);
+      } else {
+        *kind = kEntryFold;
+        *off = uint64_t(h);
+      }
+      return true;
+    }
+  }
+  return false;
+}
+EDV_HD uint64_t merkle_walk_length(MerkleProofWalk w) {
+  uint64_t len = w.seed ? 1 : 0;
+  for (; w.last > 0; w.node >>= 1, w.last >>= 1)
+    if ((w.node & 1) || w.node < w.last) len++;
+  return len;
+}
+// entries of PATH(m, D[n]), m < n, and of PROOF(first, D[second]), 1 <= first <= second
+EDV_HD uint64_t merkle_inclusion_length(uint64_t m, uint64_t n) { return merkle_walk_length(merkle_inclusion_walk(m, n)); }
+EDV_HD uint64_t merkle_consistency_length(uint64_t first, uint64_t second) {
+  return merkle_walk_length(merkle_consistency_walk(first, second));
+}
+// The positions of a proof's entries in output order (the pair as above): kind
+// and byte offset (kEntryFold: the height) per entry, at most kMerkleMaxProof.
+// Returns the count.  Pure index arithmetic: any size up to 2^62 without a store.
+EDV_HD int merkle_proof_positions(bool consistency, uint64_t a, uint64_t n, uint8_t* kind, uint64_t* off) {
+  MerkleProofWalk w = consistency ? merkle_consistency_walk(a, n) : merkle_inclusion_walk(a, n);
+  int e = 0;
+  while (merkle_walk_next(w, kind + e, off + e)) e++;
+  return e;
+}
+// the stored entry of hashes(n) for set bit b of n
+EDV_HD const uint32_t* merkle_store_entry(const uint32_t* leaf_store, const uint32_t* node_store, uint64_t n, int b) {
+  const uint64_t k = (n >> b) - 1;
+  return b == 0 ? leaf_store + 8 * k : node_store + 8 * (merkle_store_pos(b, k) - 1);
+}
+// MTH(D[0:n]) into acc, n >= 1, folded from the lowest set bit up; fold_slot
+// (or null) takes the accumulator before the first bit at or above fold_h goes
+// in.  Without want_root the fold stops there.
+EDV_HD void merkle_fold_store(uint32_t acc[8], const uint32_t* leaf_store, const uint32_t* node_store, uint64_t n,
+                              int fold_h, uint32_t* fold_slot, bool want_root) {
+  uint64_t bits = n;
+  int b = __builtin_ctzll(bits);
+  merkle_load_hash(acc, merkle_store_entry(leaf_store, node_store, n, b));
+  bits &= bits - 1;
+#pragma unroll 1
+  while (bits) {
+    b = __builtin_ctzll(bits);
+    bits &= bits - 1;
+    if (fold_slot && b >= fold_h) {
+      merkle_store_hash(fold_slot, acc);
+      fold_slot = nullptr;
+      if (!want_root) return;
+    }
+    uint32_t l[8], r[8];
+    merkle_load_hash(l, merkle_store_entry(leaf_store, node_store, n, b));
+    for (int w = 0; w < 8; w++) r[w] = acc[w];
+    merkle_node_hash(acc, l, r);
+  }
+}
+// One proof's entries into out (the walk's length of them, checked by the
+// caller) and, with want_root, MTH(D[0:w.n]) into root: the stored entries are
+// copied, the cut-off one comes out of the root's fold (which runs without
+// want_root only up to it).
+EDV_HD void merkle_prove_one(uint32_t root[8], const uint32_t* leaf_store, const uint32_t* node_store, MerkleProofWalk w,
+                             uint32_t* out, bool want_root) {
+  const uint64_t n = w.n;
+  uint32_t* fold_slot = nullptr;
+  int fold_h = 64;
+  uint8_t kind;
+  uint64_t off;
+#pragma unroll 1
+  while (merkle_walk_next(w, &kind, &off)) {
+    if (kind == kEntryFold) {
+      fold_slot = out;
+      fold_h = int(off);
+    } else {
+      merkle_copy_hash(out, (kind == kEntryLeaf ? leaf_store : node_store) + off / 4);
+    }
+    out += 8;
+  }
+  if (want_root || fold_slot) merkle_fold_store(root, leaf_store, node_store, n, fold_h, fold_slot, want_root);
+}
+EDV_HD void merkle_store_hash_or_zero(uint32_t* dst, uint32_t H[8], bool ok) {
+  if (!ok) {
+#pragma unroll
+    for (int w = 0; w < 8; w++) H[w] = 0;
+  }
+  merkle_store_hash(dst, H);
+}
+
+// One batch of inclusion proofs out of a store of store_leaves leaves (and
+// merkle_node_count(store_leaves) nodes).  Proof i goes to entries
+// [proof_off[i], proof_off[i + 1]) - proof_base of `proofs`, the layout the
+// verify kernels read.  RANGE, then SPACE (the slot is not the proof's length:
+// nothing written there), then OK.  No store position at or past the counts is
+// read: every entry of a proof in the tree of tree_size <= store_leaves leaves
+// is a subtree that ends at or before tree_size.
+struct MerkleProveInclusion {
+  uint64_t n;
+  const uint32_t* leaf_store;
+  const uint32_t* node_store;
+  uint64_t store_leaves;
+  const uint64_t* leaf_index;
+  const uint64_t* tree_size;
+  const uint64_t* proof_off;
+  uint64_t proof_base;
+  uint32_t* proofs;
+  uint8_t* status;
+  uint32_t* roots;            // MTH(D[0:tree_size]) at 8 i, zeros unless OK; or null
+  uint32_t* leaf_hashes_out;  // the leaf's stored hash at 8 i, zeros unless OK; or null
+};
+inline MerkleProveInclusion merkle_prove_inclusion_args(const void* leaf_store, const void* node_store,
+                                                        uint64_t store_leaves, const uint64_t* leaf_index,
+                                                        const uint64_t* tree_size, const uint64_t* proof_off,
+                                                        uint64_t proof_base, uint64_t n, void* proofs, uint8_t* status,
+                                                        void* roots, void* leaf_hashes_out) {
+  using H = uint32_t*;
+  return {n, static_cast<const uint32_t*>(leaf_store), static_cast<const uint32_t*>(node_store), store_leaves,
+          leaf_index, tree_size, proof_off, proof_base, H(proofs), status, H(roots), H(leaf_hashes_out)};
+}
+EDV_HD uint8_t merkle_prove_inclusion_status(uint64_t idx, uint64_t size, uint64_t store_leaves, uint64_t slot) {
+  if (idx >= size || size > store_leaves) return kProofRange;
+  return slot == merkle_inclusion_length(idx, size) ? kProofOk : kProofSpace;
+}
+EDV_HD void merkle_prove_inclusion_lane(const MerkleProveInclusion& a, uint64_t i) {
+  const uint64_t idx = a.leaf_index[i], size = a.tree_size[i];
+  const uint64_t p0 = a.proof_off[i], p1 = a.proof_off[i + 1];
+  const uint8_t st = merkle_prove_inclusion_status(idx, size, a.store_leaves, p1 - p0);
+  const bool ok = st == kProofOk;
+  uint32_t root[8];
+  if (ok)
+    merkle_prove_one(root, a.leaf_store, a.node_store, merkle_inclusion_walk(idx, size),
+                     a.proofs + 8 * (p0 - a.proof_base), a.roots != nullptr);
+  a.status[i] = st;
+  if (a.roots) merkle_store_hash_or_zero(a.roots + 8 * i, root, ok);
+  if (a.leaf_hashes_out) {
+    if (ok)
+      merkle_copy_hash(a.leaf_hashes_out + 8 * i, a.leaf_store + 8 * idx);
+    else
+      merkle_store_hash_or_zero(a.leaf_hashes_out + 8 * i, root, false);
+  }
+}
+
+// ... and of consistency proofs PROOF(first, D[second]).  RANGE: first == 0
+// (the recursive definition never ends there), first > second, second >
+// store_leaves; first == second is OK with no entries.  The old root is a fold
+// of its own over the same store, popcount(first) - 1 hashes.
+struct MerkleProveConsistency {
+  uint64_t n;
+  const uint32_t* leaf_store;
+  const uint32_t* node_store;
+  uint64_t store_leaves;
+  const uint64_t* first;
+  const uint64_t* second;
+  const uint64_t* proof_off;
+  uint64_t proof_base;
+  uint32_t* proofs;
+  uint8_t* status;
+  uint32_t* old_roots;  // MTH(D[0:first]) at 8 i, zeros unless OK; or null
+  uint32_t* new_roots;  // MTH(D[0:second])
+};
+inline MerkleProveConsistency merkle_prove_consistency_args(const void* leaf_store, const void* node_store,
+                                                            uint64_t store_leaves, const uint64_t* first,
+                                                            const uint64_t* second, const uint64_t* proof_off,
+                                                            uint64_t proof_base, uint64_t n, void* proofs,
+                                                            uint8_t* status, void* old_roots, void* new_roots) {
+  using H = uint32_t*;
+  return {n, static_cast<const uint32_t*>(leaf_store), static_cast<const uint32_t*>(node_store), store_leaves,
+          first, second, proof_off, proof_base, H(proofs), status, H(old_roots), H(new_roots)};
+}
+EDV_HD uint8_t merkle_prove_consistency_status(uint64_t first, uint64_t second, uint64_t store_leaves, uint64_t slot) {
+  if (first == 0 || first > second || second > store_leaves) return kProofRange;
+  return slot == merkle_consistency_length(first, second) ? kProofOk : kProofSpace;
+}
+EDV_HD void merkle_prove_consistency_lane(const MerkleProveConsistency& a, uint64_t i) {
+  const uint64_t first = a.first[i], second = a.second[i];
+  const uint64_t p0 = a.proof_off[i], p1 = a.proof_off[i + 1];
+  const uint8_t st = merkle_prove_consistency_status(first, second, a.store_leaves, p1 - p0);
+  const bool ok = st == kProofOk;
+  uint32_t root[8];
+  if (ok)
+    merkle_prove_one(root, a.leaf_store, a.node_store, merkle_consistency_walk(first, second),
+                     a.proofs + 8 * (p0 - a.proof_base), a.new_roots != nullptr);
+  a.status[i] = st;
+  if (a.new_roots) merkle_store_hash_or_zero(a.new_roots + 8 * i, root, ok);
+  if (a.old_roots) {
+    if (ok) merkle_fold_store(root, a.leaf_store, a.node_store, first, 64, nullptr, true);
+    merkle_store_hash_or_zero(a.old_roots + 8 * i, root, ok);
   }
 }
 

@@ -79,6 +79,21 @@ __global__ __launch_bounds__(kMerkleAppendLanes) void edv_merkle_verify_consiste
   if (i < a.n) merkle_verify_consistency_lane(a, i);
 }
 
+// Row f-8: one lane makes one proof out of the stored hashes
+// (merkle_prove_inclusion_lane / merkle_prove_consistency_lane): its stored
+// entries are 32-byte copies, the one cut-off entry and the tree head come out
+// of one fold of popcount(tree_size) - 1 node hashes.  The same shape again: no
+// LDS, no lane talks to another, 64-lane workgroups; lanes of a wave differ in
+// trip count through popcount(tree_size) and rejoin at the status store.
+__global__ __launch_bounds__(kMerkleAppendLanes) void edv_merkle_prove_inclusion_kernel(MerkleProveInclusion a) {
+  const uint64_t i = uint64_t(blockIdx.x) * kMerkleAppendLanes + threadIdx.x;
+  if (i < a.n) merkle_prove_inclusion_lane(a, i);
+}
+__global__ __launch_bounds__(kMerkleAppendLanes) void edv_merkle_prove_consistency_kernel(MerkleProveConsistency a) {
+  const uint64_t i = uint64_t(blockIdx.x) * kMerkleAppendLanes + threadIdx.x;
+  if (i < a.n) merkle_prove_consistency_lane(a, i);
+}
+
 }  // namespace
 
 namespace edv {
@@ -122,6 +137,20 @@ hipError_t launch_merkle_verify_consistency_kernel(hipStream_t s, const MerkleVe
   if (a.n == 0) return hipSuccess;
   const uint64_t blocks = (a.n + kMerkleAppendLanes - 1) / kMerkleAppendLanes;
   edv_merkle_verify_consistency_kernel<<<dim3(unsigned(blocks)), dim3(kMerkleAppendLanes), 0, s>>>(a);
+  return hipGetLastError();
+}
+
+hipError_t launch_merkle_prove_inclusion_kernel(hipStream_t s, const MerkleProveInclusion& a) {
+  if (a.n == 0) return hipSuccess;
+  const uint64_t blocks = (a.n + kMerkleAppendLanes - 1) / kMerkleAppendLanes;
+  edv_merkle_prove_inclusion_kernel<<<dim3(unsigned(blocks)), dim3(kMerkleAppendLanes), 0, s>>>(a);
+  return hipGetLastError();
+}
+
+hipError_t launch_merkle_prove_consistency_kernel(hipStream_t s, const MerkleProveConsistency& a) {
+  if (a.n == 0) return hipSuccess;
+  const uint64_t blocks = (a.n + kMerkleAppendLanes - 1) / kMerkleAppendLanes;
+  edv_merkle_prove_consistency_kernel<<<dim3(unsigned(blocks)), dim3(kMerkleAppendLanes), 0, s>>>(a);
   return hipGetLastError();
 }
 

@@ -1450,6 +1450,51 @@ int run_verify_consistency_host(DevCtx& c, const uint64_t* old_size, const uint6
   });
 }
 
+// ---- proof generation (edv_merkle.h, row f-8).  The host forms: the store
+// prefix the largest valid tree size reads, the three 64-bit arrays and the
+// slots' window [off[0], off[n]) staged in the mp_* buffers
+// (merkle_prove_needs; the slots go up too, so what no lane writes comes back
+// as the caller had it), the device forms' launch on the library stream, the
+// slots, the statuses and the outputs asked for copied back, synchronous.
+// Caller holds c.mu and has checked the arguments.  a / b: leaf_index /
+// tree_size or first / second; out1 / out2: roots / leaf hashes or old / new roots.
+template <bool kConsistency>
+int run_prove_host(DevCtx& c, const uint8_t* leaf_store, const uint8_t* node_store, uint64_t store_leaves,
+                   const uint64_t* a, const uint64_t* b, const uint64_t* proof_off, uint64_t n, uint8_t* proofs,
+                   uint8_t* status, uint8_t* out1, uint8_t* out2) {
+  MerkleBufs& m = c.mk;
+  const hipStream_t s = c.stream;
+  const uint64_t prefix = merkle_prove_prefix(kConsistency, a, b, n, store_leaves);
+  const uint64_t nodes = prefix ? merkle_node_count(prefix) : 0, pbytes = 32 * (proof_off[n] - proof_off[0]);
+  if (const int err = m.ensure(merkle_prove_needs(n, prefix, pbytes / 32, out1, out2))) return err;
+  if (prefix) HIPOK(hipMemcpyAsync(m.at(mp_leaves), leaf_store, 32 * prefix, hipMemcpyHostToDevice, s), "h2d leaf store");
+  if (nodes) HIPOK(hipMemcpyAsync(m.at(mp_nodes), node_store, 32 * nodes, hipMemcpyHostToDevice, s), "h2d node store");
+  if (pbytes) HIPOK(hipMemcpyAsync(m.at(mp_proofs), proofs + 32 * proof_off[0], pbytes, hipMemcpyHostToDevice, s), "h2d slots");
+  WordStage w{m.at<uint64_t>(mp_words), s};
+  const uint64_t *d_a = w.put(a, n), *d_b = w.put(b, n), *d_poff = w.put(proof_off, n + 1);
+  HIPOK(w.e, "h2d proof words");
+  const MerkleProveOut o = merkle_prove_out(n, out1, out2);
+  uint8_t *d_out = m.at(mp_out), *d_1 = out1 ? d_out + o.first : nullptr, *d_2 = out2 ? d_out + o.second : nullptr,
+          *d_status = d_out + o.status;
+  // the staged prefix is the store the lanes see: a valid pair reads nothing past it
+  if (kConsistency)
+    HIPOK(launch_merkle_prove_consistency_kernel(
+              s, merkle_prove_consistency_args(m.at(mp_leaves), m.at(mp_nodes), prefix, d_a, d_b, d_poff, proof_off[0], n,
+                                               m.at(mp_proofs), d_status, d_1, d_2)),
+          "merkle prove launch");
+  else
+    HIPOK(launch_merkle_prove_inclusion_kernel(
+              s, merkle_prove_inclusion_args(m.at(mp_leaves), m.at(mp_nodes), prefix, d_a, d_b, d_poff, proof_off[0], n,
+                                             m.at(mp_proofs), d_status, d_1, d_2)),
+          "merkle prove launch");
+  if (pbytes) HIPOK(hipMemcpyAsync(proofs + 32 * proof_off[0], m.at(mp_proofs), pbytes, hipMemcpyDeviceToHost, s), "d2h proofs");
+  HIPOK(hipMemcpyAsync(status, d_status, n, hipMemcpyDeviceToHost, s), "d2h proof status");
+  if (out1) HIPOK(hipMemcpyAsync(out1, d_1, 32 * n, hipMemcpyDeviceToHost, s), "d2h roots");
+  if (out2) HIPOK(hipMemcpyAsync(out2, d_2, 32 * n, hipMemcpyDeviceToHost, s), "d2h roots");
+  HIPOK(hipStreamSynchronize(s), "stream sync");
+  return 0;
+}
+
 // Asynchronous host path.  Wait for a slot's batch and hand over its verdicts.
 void async_fail(DevCtx& c, DevCtx::AsyncSlot& s) {
   c.ledger.fail(s.ticket);
@@ -2406,6 +2451,113 @@ int edv_merkle_verify_consistency_dev(const uint64_t* d_old_size, const uint64_t
         "merkle verify launch");
   if (!stream) HIPOK(hipStreamSynchronize(s), "stream sync");
   return 0;
+}
+
+// Proof generation (row f-8).  The offset helpers touch no device.
+static int prove_offsets(bool consistency, const uint64_t* a, const uint64_t* b, uint64_t n, uint64_t store_leaves,
+                         uint64_t* proof_off) {
+  g_err.clear();
+  if (!proof_off || (n && (!a || !b))) return set_err(EDV_E_ARG, "merkle prove: null pointer");
+  merkle_prove_offsets(consistency, a, b, n, store_leaves, proof_off);
+  return 0;
+}
+int edv_merkle_inclusion_offsets(const uint64_t* leaf_index, const uint64_t* tree_size, uint64_t n, uint64_t store_leaves,
+                                 uint64_t* proof_off) {
+  return prove_offsets(false, leaf_index, tree_size, n, store_leaves, proof_off);
+}
+int edv_merkle_consistency_offsets(const uint64_t* first, const uint64_t* second, uint64_t n, uint64_t store_leaves,
+                                   uint64_t* proof_off) {
+  return prove_offsets(true, first, second, n, store_leaves, proof_off);
+}
+
+// What both forms of a prove call check before anything is launched or written; *empty: n = 0
+static int check_prove_args(uint64_t n, uint64_t store_leaves, const void* leaf_store, const void* node_store,
+                            std::initializer_list<const void*> required, bool* empty) {
+  *empty = n == 0;
+  if (n > EDV_MERKLE_MAX_LEAVES) return set_err(EDV_E_ARG, "merkle prove: more than EDV_MERKLE_MAX_LEAVES proofs");
+  if (store_leaves > kMerkleMaxSize) return set_err(EDV_E_ARG, "merkle prove: store_leaves above 2^62");
+  if (n)
+    for (const void* p : required)
+      if (!p) return set_err(EDV_E_ARG, "merkle prove: null pointer");
+  if (store_leaves && !leaf_store) return set_err(EDV_E_ARG, "merkle prove: null leaf_store");
+  if (store_leaves > 1 && !node_store) return set_err(EDV_E_ARG, "merkle prove: null node_store");
+  return 0;
+}
+
+static int prove_host(bool consistency, const uint8_t* leaf_store, const uint8_t* node_store, uint64_t store_leaves,
+                      const uint64_t* a, const uint64_t* b, const uint64_t* proof_off, uint64_t n, uint8_t* proofs,
+                      uint8_t* status, uint8_t* out1, uint8_t* out2, int device) {
+  g_err.clear();
+  int err;
+  bool empty;
+  if ((err = check_prove_args(n, store_leaves, leaf_store, node_store, {a, b, proof_off, proofs, status}, &empty)))
+    return err;
+  if (empty) return 0;
+  if ((err = check_offsets(proof_off, n))) return err;
+  CtxLock cl(device);
+  if (cl.err) return cl.err;
+  memset(status, EDV_PROOF_UNVERIFIED, n);  // a call that fails part-way leaves no proof marked as made
+  return consistency ? run_prove_host<true>(*cl.c, leaf_store, node_store, store_leaves, a, b, proof_off, n, proofs,
+                                            status, out1, out2)
+                     : run_prove_host<false>(*cl.c, leaf_store, node_store, store_leaves, a, b, proof_off, n, proofs,
+                                             status, out1, out2);
+}
+int edv_merkle_prove_inclusion(const uint8_t* leaf_store, const uint8_t* node_store, uint64_t store_leaves,
+                               const uint64_t* leaf_index, const uint64_t* tree_size, const uint64_t* proof_off,
+                               uint64_t n, uint8_t* proofs, uint8_t* status, uint8_t* roots, uint8_t* leaf_hashes_out,
+                               int device) {
+  return prove_host(false, leaf_store, node_store, store_leaves, leaf_index, tree_size, proof_off, n, proofs, status,
+                           roots, leaf_hashes_out, device);
+}
+int edv_merkle_prove_consistency(const uint8_t* leaf_store, const uint8_t* node_store, uint64_t store_leaves,
+                                 const uint64_t* first, const uint64_t* second, const uint64_t* proof_off, uint64_t n,
+                                 uint8_t* proofs, uint8_t* status, uint8_t* old_roots, uint8_t* new_roots, int device) {
+  return prove_host(true, leaf_store, node_store, store_leaves, first, second, proof_off, n, proofs, status, old_roots,
+                          new_roots, device);
+}
+
+static int prove_dev(bool consistency, const uint8_t* d_leaf_store, const uint8_t* d_node_store,
+                     uint64_t store_leaves, const uint64_t* d_a, const uint64_t* d_b, const uint64_t* d_proof_off,
+                     uint64_t proof_base, uint64_t n, uint8_t* d_proofs, uint8_t* d_status, uint8_t* d_out1, uint8_t* d_out2, int device, void* stream) {
+  g_err.clear();
+  int err;
+  bool empty;
+  if ((err = check_prove_args(n, store_leaves, d_leaf_store, d_node_store, {d_a, d_b, d_proof_off, d_proofs, d_status},
+                              &empty)))
+    return err;
+  // the lanes read sizes, indices and offsets as 64-bit words and every hash as two 16-byte vectors
+  if ((err = check_proof_align({d_a, d_b, d_proof_off}, {d_leaf_store, d_node_store, d_proofs, d_out1, d_out2}))) return err;
+  if (empty) return 0;
+  CtxLock cl(device);
+  if (cl.err) return cl.err;
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : cl.c->stream;
+  if (consistency)
+    HIPOK(launch_merkle_prove_consistency_kernel(
+              s, merkle_prove_consistency_args(d_leaf_store, d_node_store, store_leaves, d_a, d_b, d_proof_off, proof_base,
+                                               n, d_proofs, d_status, d_out1, d_out2)),
+          "merkle prove launch");
+  else
+    HIPOK(launch_merkle_prove_inclusion_kernel(
+              s, merkle_prove_inclusion_args(d_leaf_store, d_node_store, store_leaves, d_a, d_b, d_proof_off, proof_base,
+                                             n, d_proofs, d_status, d_out1, d_out2)),
+          "merkle prove launch");
+  if (!stream) HIPOK(hipStreamSynchronize(s), "stream sync");
+  return 0;
+}
+int edv_merkle_prove_inclusion_dev(const uint8_t* d_leaf_store, const uint8_t* d_node_store, uint64_t store_leaves,
+                                   const uint64_t* d_leaf_index, const uint64_t* d_tree_size,
+                                   const uint64_t* d_proof_off, uint64_t proof_base, uint64_t n, uint8_t* d_proofs,
+                                   uint8_t* d_status, uint8_t* d_roots, uint8_t* d_leaf_hashes_out, int device,
+                                   void* stream) {
+  return prove_dev(false, d_leaf_store, d_node_store, store_leaves, d_leaf_index, d_tree_size, d_proof_off, proof_base, n,
+                          d_proofs, d_status, d_roots, d_leaf_hashes_out, device, stream);
+}
+int edv_merkle_prove_consistency_dev(const uint8_t* d_leaf_store, const uint8_t* d_node_store, uint64_t store_leaves,
+                                     const uint64_t* d_first, const uint64_t* d_second, const uint64_t* d_proof_off,
+                                     uint64_t proof_base, uint64_t n, uint8_t* d_proofs, uint8_t* d_status,
+                                     uint8_t* d_old_roots, uint8_t* d_new_roots, int device, void* stream) {
+  return prove_dev(true, d_leaf_store, d_node_store, store_leaves, d_first, d_second, d_proof_off, proof_base, n, d_proofs,
+                         d_status, d_old_roots, d_new_roots, device, stream);
 }
 
 int edv_verify_batch_dev_flags(const uint8_t* d_sigs, const uint8_t* d_pks, const uint8_t* d_msgs,

@@ -108,6 +108,15 @@ def lib():
         h.edv_merkle_verify_consistency.restype = ctypes.c_int
         h.edv_merkle_verify_consistency_dev.argtypes = [vp] * 6 + [u64, u64, vp, vp, ctypes.c_int, vp]
         h.edv_merkle_verify_consistency_dev.restype = ctypes.c_int
+        for f in (h.edv_merkle_inclusion_offsets, h.edv_merkle_consistency_offsets):
+            f.argtypes = [vp, vp, u64, u64, vp]
+            f.restype = ctypes.c_int
+        for f in (h.edv_merkle_prove_inclusion, h.edv_merkle_prove_consistency):
+            f.argtypes = [vp, vp, u64, vp, vp, vp, u64, vp, vp, vp, vp, ctypes.c_int]
+            f.restype = ctypes.c_int
+        for f in (h.edv_merkle_prove_inclusion_dev, h.edv_merkle_prove_consistency_dev):
+            f.argtypes = [vp, vp, u64, vp, vp, vp, u64, u64, vp, vp, vp, vp, ctypes.c_int, vp]
+            f.restype = ctypes.c_int
         h.edv_verify_batch_dev_flags.argtypes = [vp, vp, vp, vp, u64, u64, vp, ctypes.c_int, vp, ctypes.c_uint32]
         h.edv_verify_batch_dev_flags.restype = ctypes.c_int
         h.edv_verify_batch_dev_pipelined.argtypes = [vp, vp, vp, vp, u64, u64, vp, ctypes.c_int, ctypes.c_uint32]
@@ -678,6 +687,108 @@ def merkle_verify_consistency_device(d_old_size, d_new_size, d_old_roots, d_new_
     """Device-resident form (pointers are ints, None = NULL); async on `stream` if given."""
     _check(lib().edv_merkle_verify_consistency_dev(d_old_size, d_new_size, d_old_roots, d_new_roots, d_proofs,
                                                    d_proof_off, proof_base, n, d_status, d_computed, device, stream))
+
+
+# proof generation (row f-8)
+PROOF_SPACE = 7        # proof generation only: the slot's length is not the proof's; nothing else written
+
+
+def _prove_pairs(a, b, what_a, what_b):
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    b = np.ascontiguousarray(b, dtype=np.uint64)
+    if a.ndim != 1 or b.ndim != 1 or len(a) != len(b):
+        raise ValueError("%s and %s must hold one entry per proof" % (what_a, what_b))
+    if len(a) > MERKLE_MAX_LEAVES:
+        raise ValueError("more than MERKLE_MAX_LEAVES proofs in one call")
+    return a, b, len(a)
+
+
+def _prove_offsets(call, a, b, store_leaves):
+    n = len(a)
+    off = np.zeros(n + 1, dtype=np.uint64)
+    _check(call(a.ctypes.data, b.ctypes.data, n, int(store_leaves), off.ctypes.data))
+    return off
+
+
+def merkle_inclusion_offsets(leaf_index, tree_size, store_leaves: int) -> np.ndarray:
+    """The n + 1 packed slot offsets (in entries, from 0) of the audit paths of
+    (leaf_index[i], tree_size[i]) over a store of store_leaves leaves; a pair
+    that merkle_prove_inclusion answers with PROOF_RANGE takes no entries
+    (edv_merkle_inclusion_offsets; no device is touched)."""
+    a, b, _ = _prove_pairs(leaf_index, tree_size, "leaf_index", "tree_size")
+    return _prove_offsets(lib().edv_merkle_inclusion_offsets, a, b, store_leaves)
+
+
+def merkle_consistency_offsets(first, second, store_leaves: int) -> np.ndarray:
+    """As merkle_inclusion_offsets, for PROOF(first[i], D[0:second[i]])."""
+    a, b, _ = _prove_pairs(first, second, "first", "second")
+    return _prove_offsets(lib().edv_merkle_consistency_offsets, a, b, store_leaves)
+
+
+def _prove_host(call, offsets, leaf_store, node_store, store_leaves, a, b, proof_off, want1, want2, device):
+    store_leaves = int(store_leaves)
+    if not 0 <= store_leaves <= MERKLE_MAX_SIZE:
+        raise ValueError("store_leaves must be in [0, 2^62]")
+    leaf_store = _u8(leaf_store, "leaf_store", 32 * store_leaves)
+    node_store = _u8(node_store, "node_store", 32 * (store_leaves - bin(store_leaves).count("1")))
+    n = len(a)
+    off = offsets(a, b, store_leaves) if proof_off is None else _u64(proof_off, "proof_off", n + 1)
+    if n and np.any(off[1:] < off[:-1]):
+        raise ValueError("proof_off must not decrease")
+    proofs = np.zeros((int(off[-1]), 32), dtype=np.uint8)
+    status = np.zeros(n, dtype=np.uint8)
+    out1 = np.zeros((n, 32), dtype=np.uint8) if want1 else None
+    out2 = np.zeros((n, 32), dtype=np.uint8) if want2 else None
+    _check(call(leaf_store.ctypes.data, node_store.ctypes.data, store_leaves, a.ctypes.data, b.ctypes.data,
+                off.ctypes.data, n, proofs.ctypes.data, status.ctypes.data, _ptr(out1), _ptr(out2), device))
+    return proofs, off, status, out1, out2
+
+
+def merkle_prove_inclusion(leaf_store, node_store, store_leaves, leaf_index, tree_size, proof_off=None,
+                           want_roots=True, want_leaf_hashes=False, device: int = 0):
+    """n audit paths out of a hash store in host memory (edv_merkle_prove_inclusion,
+    row f-8).  The call copies the store prefix it reads to the device every
+    time: for small stores and callers without device memory.
+
+    leaf_store / node_store: the store's hashes (bytes or uint8 arrays,
+    store_leaves x 32 and (store_leaves - popcount(store_leaves)) x 32 bytes at
+    least); leaf_index / tree_size: n integers below 2^64; proof_off: n + 1
+    slot offsets in entries (default: merkle_inclusion_offsets, the exact fit).
+    Returns (proofs, proof_off, status, roots, leaf_hashes): the packed
+    (entries, 32) proofs in the verifier's layout, n PROOF_* bytes (OK, RANGE
+    or SPACE), and the (n, 32) tree heads and stored leaf hashes (None unless
+    wanted; zeros where the status is not OK)."""
+    a, b, _ = _prove_pairs(leaf_index, tree_size, "leaf_index", "tree_size")
+    return _prove_host(lib().edv_merkle_prove_inclusion, merkle_inclusion_offsets, leaf_store, node_store,
+                       store_leaves, a, b, proof_off, want_roots, want_leaf_hashes, device)
+
+
+def merkle_prove_consistency(leaf_store, node_store, store_leaves, first, second, proof_off=None, want_roots=True,
+                             device: int = 0):
+    """n consistency proofs PROOF(first, D[0:second]) out of a hash store in
+    host memory (edv_merkle_prove_consistency).  Returns (proofs, proof_off,
+    status, old_roots, new_roots), as merkle_prove_inclusion."""
+    a, b, _ = _prove_pairs(first, second, "first", "second")
+    return _prove_host(lib().edv_merkle_prove_consistency, merkle_consistency_offsets, leaf_store, node_store,
+                       store_leaves, a, b, proof_off, want_roots, want_roots, device)
+
+
+def merkle_prove_inclusion_device(d_leaf_store, d_node_store, store_leaves, d_leaf_index, d_tree_size, d_proof_off, n,
+                                  d_proofs, d_status, d_roots=None, d_leaf_hashes_out=None, device=0, proof_base=0,
+                                  stream=None):
+    """Device-resident form (pointers are ints, None = NULL); async on `stream` if given."""
+    _check(lib().edv_merkle_prove_inclusion_dev(d_leaf_store, d_node_store, store_leaves, d_leaf_index, d_tree_size,
+                                                d_proof_off, proof_base, n, d_proofs, d_status, d_roots,
+                                                d_leaf_hashes_out, device, stream))
+
+
+def merkle_prove_consistency_device(d_leaf_store, d_node_store, store_leaves, d_first, d_second, d_proof_off, n,
+                                    d_proofs, d_status, d_old_roots=None, d_new_roots=None, device=0, proof_base=0,
+                                    stream=None):
+    """Device-resident form (pointers are ints, None = NULL); async on `stream` if given."""
+    _check(lib().edv_merkle_prove_consistency_dev(d_leaf_store, d_node_store, store_leaves, d_first, d_second,
+                                                  d_proof_off, proof_base, n, d_proofs, d_status, d_old_roots,
+                                                  d_new_roots, device, stream))
 
 
 def verify_detached_batch(items, device_mask: int = 0):

@@ -12,6 +12,8 @@ classes, written from their semantics:
   plenum/common/ledger.py:98-137          discardTxns, treeWithAppliedTxns
   plenum/client/client.py:846-873         verifyMerkleProof -> verify_merkle_proofs (row f-7)
   plenum/common/ledger_manager.py:564-609 hasValidCatchupReplies -> Ledger.verify_catchup_txns
+  plenum/server/node.py:3024-3034         getReplyFromLedger: merkleInfo per reply -> merkleInfoBatch (row f-8)
+  plenum/common/ledger_manager.py:995-998 a consistency proof and both roots -> consistency_proofs (row f-8)
 
 commitTxns(count) is one CompactMerkleTree.append_batch call
 (edv_merkle_append_batch from merkle.MIN_DEVICE_APPEND_LEAVES transactions
@@ -149,6 +151,33 @@ class Ledger:
             raise ValueError("seqNo must be > 0, got %r" % (seqNo,))
         return {"rootHash": self.hashToStr(self.tree.merkle_tree_hash(0, seqNo)),
                 "auditPath": [self.hashToStr(h) for h in self.tree.inclusion_proof(seqNo - 1, seqNo)]}
+
+    # ---- reads, a batch at a time (row f-8)
+    def merkle_proofs(self, seqNos, on_device=None):
+        """The raw ProofBatch behind merkleInfoBatch: audit paths, tree heads
+        and leaf hashes as packed arrays, no base58.  on_device None: the
+        ledger's own setting, then the tree's routing (the device with a
+        merkle.DeviceHashStore, from merkle.MIN_DEVICE_PROVE_PROOFS proofs on)."""
+        return self.tree.merkle_info_batch(seqNos, on_device=self.on_device if on_device is None else on_device,
+                                           device=self.device)
+
+    def merkleInfoBatch(self, seqNos, on_device=None):
+        """[self.merkleInfo(s) for s in seqNos], from one batched proof call
+        (plenum/server/node.py:3024-3034 asks once per reply)."""
+        batch = self.merkle_proofs(seqNos, on_device)
+        return [{"rootHash": self.hashToStr(batch.roots[i].tobytes()),
+                 "auditPath": [self.hashToStr(h) for h in path]} for i, path in enumerate(batch)]
+
+    def consistency_proofs(self, pairs, on_device=None):
+        """Per (first, second): the consistency proof and both root hashes, as
+        catch-up computes them one pair at a time
+        (plenum/common/ledger_manager.py:995-998): a list of dicts with
+        `proof` (base58 strings), `oldRootHash` and `newRootHash`."""
+        batch = self.tree.consistency_proof_batch(pairs, on_device=self.on_device if on_device is None else on_device,
+                                                  device=self.device)
+        return [{"proof": [self.hashToStr(h) for h in proof],
+                 "oldRootHash": self.hashToStr(batch.old_roots[i].tobytes()),
+                 "newRootHash": self.hashToStr(batch.new_roots[i].tobytes())} for i, proof in enumerate(batch)]
 
     def reset(self):
         """Destructive: the log and the hash store are emptied (the tree

@@ -13,8 +13,16 @@ RFC 6962 (section 2.1) and the append semantics:
 contents.  (The reference's own extend leaves its hash store in another state,
 which Ledger never uses; that state is not reproduced.)  With the device it is
 one edv_merkle_extend call per EDV_MERKLE_MAX_LEAVES leaves (gfx950 kernels
-edv_merkle_pass_kernel / edv_merkle_finish_kernel); `append`, the proofs and
-everything that reads the store stay on the host.
+edv_merkle_pass_kernel / edv_merkle_finish_kernel); `append` and the single
+proofs, which read the store one hash at a time, stay on the host.
+
+The batched reads (row f-8: ledger/ledger.py:197-206 merkleInfo per reply,
+plenum/common/ledger_manager.py:448-452 consistency proofs in catch-up) are
+`inclusion_proof_batch`, `consistency_proof_batch` and `merkle_info_batch`:
+with a `DeviceHashStore`, whose contents are mirrored on the device, one
+edv_merkle_prove_*_dev call for the batch (kernels
+edv_merkle_prove_inclusion_kernel / edv_merkle_prove_consistency_kernel),
+returning a ProofBatch in the layout the batched verification reads.
 
 `append_batch` (row f-6) is `extend` that also returns what each `append`
 returns (ledger/ledger.py:145-155: the audit path, and the root hash read after
@@ -60,6 +68,15 @@ MIN_DEVICE_APPEND_LEAVES = 256
 # paths of 3 entries, the narrowest margin of the table, and 169 us against
 # 332 us onto 2^20 + 12,345 leaves; nothing below 64 was measured)
 MIN_DEVICE_VERIFY_PROOFS = 64
+
+
+# *_proof_batch / merkle_info_batch(on_device=None) over a DeviceHashStore take
+# the device from this many proofs on: the smallest size measured, at which the
+# route through the store's mirror, outputs copied back, already beats the host
+# loop of single calls on both trees (profiles/r10/merkle_prove_bench.json,
+# "crossover": 113 us against 187 us for 16 merkleInfo proofs on 10,000
+# leaves, 114 us against 205 us on 2^20 + 12,345; nothing below 16 was measured)
+MIN_DEVICE_PROVE_PROOFS = 16
 
 
 class ConsistencyVerificationFailed(Exception):
@@ -238,6 +255,105 @@ class MemoryHashStore:
         if pos < 1 or pos * self.HASH > len(arr):
             raise IndexError("no hash at position %r" % (pos,))
         return bytes(arr[(pos - 1) * self.HASH:pos * self.HASH])
+
+
+class DeviceHashStore(MemoryHashStore):
+    """A MemoryHashStore whose contents are mirrored in device memory, for the
+    batched proofs (row f-8).  The host bytes stay authoritative: every write
+    and read is MemoryHashStore's.  device_arrays() brings the mirror up to
+    date by uploading the tail not yet sent (the stores only grow) and returns
+    (leaf pointer, node pointer, leaf count, node count).  A mirror that has
+    become too small is replaced by one of twice the size, at least, and the
+    whole store is uploaded again from the host copy.  reset() frees the
+    device memory.  Nothing touches the device before the first
+    device_arrays(), so without a GPU this is a plain store."""
+    MIN_CAPACITY = 1 << 16  # bytes
+
+    def __init__(self, device=0):
+        self.device = device
+        self._bufs = [None, None]
+        self._work = None
+        super().__init__()
+
+    def reset(self):
+        for b in self._bufs + [self._work]:
+            if b is not None:
+                b.free()
+        self._bufs = [None, None]   # edv.DeviceBuffer of the leaf store, of the node store
+        self._sent = [0, 0]         # bytes of each the mirror holds
+        self._work = None           # the batch calls' inputs and outputs (work_area)
+        self.bytes_uploaded = 0     # in all, since the last reset
+        return super().reset()
+
+    @property
+    def device_bytes(self):
+        """Device memory held: both mirrors and the work area."""
+        return sum(b.nbytes for b in self._bufs + [self._work] if b is not None)
+
+    def device_arrays(self):
+        for k, host in enumerate((self._leafs, self._nodes)):
+            need, buf = len(host), self._bufs[k]
+            if buf is None or need > buf.nbytes:
+                cap = max(self.MIN_CAPACITY, need, 2 * (buf.nbytes if buf is not None else 0))
+                if buf is not None:
+                    buf.free()
+                buf = self._bufs[k] = edv.DeviceBuffer(cap, self.device)
+                self._sent[k] = 0
+            sent = self._sent[k]
+            if need > sent:
+                tail = np.frombuffer(host, dtype=np.uint8, count=need - sent, offset=sent)
+                edv._check(edv.lib().edv_h2d(self.device, buf.ptr + sent, tail.ctypes.data, need - sent))
+                del tail  # the bytearray may grow again
+                self.bytes_uploaded += need - sent
+                self._sent[k] = need
+        return self._bufs[0].ptr, self._bufs[1].ptr, self.leafCount, self.nodeCount
+
+    def work_area(self, nbytes):
+        """A device buffer of at least nbytes that the batch calls reuse."""
+        if self._work is None or self._work.nbytes < nbytes:
+            cap = max(self.MIN_CAPACITY, nbytes, 2 * (self._work.nbytes if self._work is not None else 0))
+            if self._work is not None:
+                self._work.free()
+            self._work = edv.DeviceBuffer(cap, self.device)
+        return self._work
+
+
+class ProofBatch:
+    """What a batched proof call returned (row f-8), in the layout the batched
+    verification takes as it is: `proofs`, an (entries, 32) uint8 array, proof i
+    being rows off[i] .. off[i + 1], lowest level first; `status`, one
+    edv.PROOF_* per proof (all PROOF_OK: a pair out of range raises instead).
+    kind "inclusion": `index` and `size` (leaf index and tree size per proof),
+    `roots` (MTH(D[0:size]), (n, 32), or None if not asked for) and
+    `leaf_hashes` (the leaves' stored hashes).  kind "consistency": `index` is
+    the older size, `size` the newer one, `old_roots` / `new_roots` their tree
+    heads.  proof(i) and iteration give a proof as a list of bytes."""
+
+    def __init__(self, kind, index, size, proofs, off, status, roots=None, leaf_hashes=None, old_roots=None,
+                 new_roots=None):
+        self.kind = kind
+        self.index, self.size = index, size
+        self.proofs, self.off, self.status = proofs, off, status
+        self.roots, self.leaf_hashes = roots, leaf_hashes
+        self.old_roots, self.new_roots = old_roots, new_roots
+
+    def __len__(self):
+        return len(self.status)
+
+    def proof(self, i):
+        if not 0 <= i < len(self.status):
+            raise IndexError(i)
+        blob = self.proofs[int(self.off[i]):int(self.off[i + 1])].tobytes()
+        return [blob[k:k + 32] for k in range(0, len(blob), 32)]
+
+    def __iter__(self):
+        blob = self.proofs.tobytes()
+        for i in range(len(self.status)):
+            yield [blob[k:k + 32] for k in range(32 * int(self.off[i]), 32 * int(self.off[i + 1]), 32)]
+
+
+def _hash_rows(hashes):
+    return np.frombuffer(b"".join(hashes), dtype=np.uint8).reshape(-1, 32)
 
 
 class CompactMerkleTree:
@@ -464,6 +580,150 @@ class CompactMerkleTree:
         if m <= k:
             return self._subproof(m, lo, lo + k, whole) + [(lo + k, hi)]
         return self._subproof(m - k, lo + k, hi, False) + [(lo, lo + k)]
+
+    # ---- reading, a batch at a time (row f-8)
+    def _store_bytes(self):
+        store = self.__hashStore
+        if isinstance(store, MemoryHashStore):
+            return store._leafs, store._nodes
+        return (b"".join(store.readLeafs(1, store.leafCount + 1)), b"".join(store.readNodes(1, store.nodeCount + 1)))
+
+    def _prove_route(self, n, on_device):
+        """"host" (the single calls in a loop), "store" (the device forms over
+        a DeviceHashStore's mirror) or "copy" (the host-buffer form, which
+        copies the store per call)."""
+        mirrored = isinstance(self.__hashStore, DeviceHashStore)
+        if on_device is None:
+            on_device = mirrored and n >= MIN_DEVICE_PROVE_PROOFS
+        if not on_device:
+            return "host"
+        if self.__hasher.hashfunc is not hashlib.sha256:
+            raise ValueError("the device proves SHA-256 trees only")
+        return "store" if mirrored else "copy"
+
+    def _checked_pairs(self, pairs, consistency):
+        """The pairs as two uint64 arrays, after the checks every route makes
+        first, so that all of them raise alike: ValueError for a pair that is
+        no proof's (leaf index not below the tree size; older size 0 or above
+        the newer one), IndexError for a tree larger than the store."""
+        if not isinstance(pairs, (list, tuple, np.ndarray)):
+            pairs = list(pairs)
+        if len(pairs) > edv.MERKLE_MAX_LEAVES:
+            raise ValueError("more than %d proofs in one call" % edv.MERKLE_MAX_LEAVES)
+        try:   # one conversion for the whole batch: integers below 2^63, which is every real tree's
+            both = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+            if (both < 0).any():
+                raise ValueError("sizes and indices must be in [0, 2^64)")
+            a, b = both[:, 0].astype(np.uint64), both[:, 1].astype(np.uint64)
+        except OverflowError:
+            pairs = [(int(x), int(y)) for x, y in pairs]
+            if any(not (_in_u64(x) and _in_u64(y)) for x, y in pairs):
+                raise ValueError("sizes and indices must be in [0, 2^64)")
+            a = np.array([p[0] for p in pairs], dtype=np.uint64)
+            b = np.array([p[1] for p in pairs], dtype=np.uint64)
+        bad = ((a == 0) | (a > b)) if consistency else (a >= b)
+        if bad.any():
+            i = int(np.flatnonzero(bad)[0])
+            raise ValueError("pair %d: %s" % (i, "the older size must be in [1, newer size]" if consistency
+                                              else "the leaf index must be below the tree size"))
+        big = b > np.uint64(self.leafCount)
+        if big.any():
+            raise IndexError("pair %d: the store has no tree of %d leaves" % (int(np.flatnonzero(big)[0]),
+                                                                              int(b[np.flatnonzero(big)[0]])))
+        return a, b
+
+    def _prove_device(self, consistency, a, b, want1, want2, device):
+        """-> (proofs, off, status, out1, out2) through the mirror of a DeviceHashStore."""
+        store, n = self.__hashStore, len(a)
+        d_leafs, d_nodes, leaves, _ = store.device_arrays()
+        off = (edv.merkle_consistency_offsets if consistency else edv.merkle_inclusion_offsets)(a, b, leaves)
+        entries = int(off[-1])
+        # words | proofs | out1 | out2 | status: every hash buffer on 32 bytes
+        wbytes = (8 * (3 * n + 1) + 31) // 32 * 32
+        o_proofs, o_1 = wbytes, wbytes + 32 * entries
+        o_2 = o_1 + (32 * n if want1 else 0)
+        o_st = o_2 + (32 * n if want2 else 0)
+        work = store.work_area(o_st + n + 32)
+        work.upload(np.concatenate([a, b, off]))
+        p = work.ptr
+        call = edv.merkle_prove_consistency_device if consistency else edv.merkle_prove_inclusion_device
+        call(d_leafs, d_nodes, leaves, p, p + 8 * n, p + 16 * n, n, p + o_proofs, p + o_st,
+             p + o_1 if want1 else None, p + o_2 if want2 else None, device=device)
+        back = work.download_at(o_proofs, o_st + n - o_proofs)
+        proofs = back[:32 * entries].reshape(-1, 32)
+        out1 = back[o_1 - o_proofs:o_1 - o_proofs + 32 * n].reshape(-1, 32) if want1 else None
+        out2 = back[o_2 - o_proofs:o_2 - o_proofs + 32 * n].reshape(-1, 32) if want2 else None
+        return proofs, off, back[o_st - o_proofs:], out1, out2
+
+    def _prove_batch(self, consistency, pairs, on_device, device, want1, want2):
+        a, b = self._checked_pairs(pairs, consistency)
+        n = len(a)
+        route = self._prove_route(n, on_device)
+        if n == 0:
+            empty = np.zeros((0, 32), np.uint8)
+            return a, b, empty, np.zeros(1, np.uint64), np.zeros(0, np.uint8), empty if want1 else None, \
+                empty if want2 else None
+        if route == "host":
+            single = self.consistency_proof if consistency else self.inclusion_proof
+            proofs = [single(int(x), int(y)) for x, y in zip(a, b)]
+            off = np.zeros(n + 1, dtype=np.uint64)
+            off[1:] = np.cumsum([len(p) for p in proofs], dtype=np.uint64)
+            out1 = out2 = None
+            if consistency:
+                if want1:
+                    out1 = _hash_rows([self.merkle_tree_hash(0, int(x)) for x in a])
+                    out2 = _hash_rows([self.merkle_tree_hash(0, int(y)) for y in b])
+            else:
+                if want1:
+                    out1 = _hash_rows([self.merkle_tree_hash(0, int(y)) for y in b])
+                if want2:
+                    out2 = _hash_rows([self.__hashStore.readLeaf(int(x) + 1) for x in a])
+            return a, b, _hash_rows([h for p in proofs for h in p]), off, np.full(n, edv.PROOF_OK, np.uint8), out1, out2
+        if route == "store":
+            proofs, off, status, out1, out2 = self._prove_device(consistency, a, b, want1, want2, device)
+        else:
+            leafs, nodes = self._store_bytes()
+            if consistency:
+                proofs, off, status, out1, out2 = edv.merkle_prove_consistency(
+                    leafs, nodes, self.leafCount, a, b, want_roots=want1, device=device)
+            else:
+                proofs, off, status, out1, out2 = edv.merkle_prove_inclusion(
+                    leafs, nodes, self.leafCount, a, b, want_roots=want1, want_leaf_hashes=want2, device=device)
+        if not (status == edv.PROOF_OK).all():   # the pairs were checked and the slots fit: not reachable
+            raise RuntimeError("proof %d came back with status %d" % (int(np.flatnonzero(status != edv.PROOF_OK)[0]),
+                                                                     int(status[status != edv.PROOF_OK][0])))
+        return a, b, proofs, off, status, out1, out2
+
+    def inclusion_proof_batch(self, pairs, on_device=None, device=0, want_roots=True):
+        """inclusion_proof(m, n) for every (m, n) of pairs, with the leaves'
+        stored hashes and (want_roots) merkle_tree_hash(0, n), as a ProofBatch.
+        on_device None: over a DeviceHashStore, the device from
+        MIN_DEVICE_PROVE_PROOFS pairs on (edv_merkle_prove_inclusion_dev over
+        the store's mirror); over any other store, the host.  True over
+        another store is edv_merkle_prove_inclusion, which copies the store
+        per call.  A pair with m >= n raises ValueError, a tree larger than the
+        store IndexError, before anything is computed."""
+        a, b, proofs, off, status, roots, leaf_hashes = self._prove_batch(False, pairs, on_device, device, want_roots,
+                                                                          True)
+        return ProofBatch("inclusion", a, b, proofs, off, status, roots=roots, leaf_hashes=leaf_hashes)
+
+    def consistency_proof_batch(self, pairs, on_device=None, device=0, want_roots=True):
+        """consistency_proof(first, second) for every pair, with both tree
+        heads (want_roots), as a ProofBatch; routed as inclusion_proof_batch.
+        first == second is the empty proof; first 0 or above second raises
+        ValueError, second above the store IndexError."""
+        a, b, proofs, off, status, old_roots, new_roots = self._prove_batch(True, pairs, on_device, device, want_roots,
+                                                                            want_roots)
+        return ProofBatch("consistency", a, b, proofs, off, status, old_roots=old_roots, new_roots=new_roots)
+
+    def merkle_info_batch(self, seq_nos, on_device=None, device=0, want_roots=True):
+        """What Ledger.merkleInfo reads for every seqNo: the audit path of leaf
+        seqNo - 1 in the tree of seqNo leaves and that tree's head."""
+        seq_nos = [int(s) for s in seq_nos]
+        for s in seq_nos:
+            if s <= 0:
+                raise ValueError("seqNo must be > 0, got %r" % (s,))
+        return self.inclusion_proof_batch([(s - 1, s) for s in seq_nos], on_device, device, want_roots)
 
     def get_tree_head(self, seq=None):
         if seq is None:
@@ -779,6 +1039,32 @@ class MerkleVerifier:
         idx = [batch.old_size + i for i in range(n)]
         return self._inclusion(leaves, None, idx, [s + 1 for s in idx], np.ascontiguousarray(batch.roots),
                                np.ascontiguousarray(batch.paths), off, on_device, device, want_computed, max_call)
+
+    def verify_proof_batch(self, batch, on_device=None, device=0, want_computed=False):
+        """Check a ProofBatch (row f-8) as it is, with no repacking: audit
+        paths against the batch's leaf hashes and tree heads, consistency
+        proofs against its old and new roots.  The batch must carry them
+        (want_roots)."""
+        proofs, off = np.ascontiguousarray(batch.proofs), np.ascontiguousarray(batch.off, dtype=np.uint64)
+        if batch.kind == "inclusion":
+            if batch.roots is None or batch.leaf_hashes is None:
+                raise ValueError("the ProofBatch holds no tree heads")
+            return self._inclusion(None, np.ascontiguousarray(batch.leaf_hashes), batch.index, batch.size,
+                                   np.ascontiguousarray(batch.roots), proofs, off, on_device, device, want_computed)
+        if batch.old_roots is None or batch.new_roots is None:
+            raise ValueError("the ProofBatch holds no tree heads")
+        n = len(batch)
+        old_roots, new_roots = np.ascontiguousarray(batch.old_roots), np.ascontiguousarray(batch.new_roots)
+        if self._device_default(n, on_device):
+            status, computed = edv.merkle_verify_consistency(batch.index, batch.size, old_roots, new_roots, proofs, off,
+                                                             want_computed=want_computed, device=device)
+            return ProofVerdicts(status, computed)
+        res = [_walk_consistency(self.hasher, int(batch.index[i]), int(batch.size[i]), old_roots[i].tobytes(),
+                                 new_roots[i].tobytes(), batch.proof(i)) for i in range(n)]
+        computed = None
+        if want_computed:
+            computed = np.frombuffer(b"".join(c for _, c in res), dtype=np.uint8).reshape(-1, 64)
+        return ProofVerdicts([st for st, _ in res], computed)
 
 
 def verify_append_batch(old_size, leaves, batch, on_device=None, device=0, max_call=None):

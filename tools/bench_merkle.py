@@ -40,6 +40,24 @@ trip count per wave).  The smallest size from which (c) beats (e) on both
 trees is MIN_DEVICE_VERIFY_PROOFS.  And 10,000 consistency proofs (m, 4096)
 of one real tree, verify_tree_consistency_batch on the device and on the host.
 
+With --leg prove: batched proof generation (row f-8), written to
+profiles/r10/merkle_prove_bench.json.  Two trees of 8-byte leaves in a
+DeviceHashStore, 10,000 leaves and 2^20 + 12,345, and three sets of 10,000
+pairs on each: merkleInfo (the last 10,000 seqNos: leaf s - 1 in the tree of s
+leaves), inclusion (random leaves in the whole tree) and consistency (random
+first <= random second):
+  a  edv_merkle_prove_*_dev           device-resident, all outputs; HIP events on a stream of the bench's own
+  v  edv_merkle_verify_*_dev          row f-7 on the proofs (a) made, device-resident, HIP events
+  b  CompactMerkleTree.*_batch(on_device=True)   through the DeviceHashStore, outputs copied back
+  c  edv_merkle_prove_*               the host-buffer form (copies the store per call)
+  e  CompactMerkleTree.*_batch(on_device=False)  the package's host loop of single calls
+with the lane efficiency of the fold (mean over waves of mean / max
+popcount - 1), (a) again with the pairs sorted by popcount(tree_size), the
+base58 encoding of the 10,000 merkleInfo replies on a line of its own, and
+(b) against (e) at 16, 64, 256 and 1,024 merkleInfo proofs, whose smallest size
+from which (b) wins on both trees is MIN_DEVICE_PROVE_PROOFS.  The routes of a
+case are timed interleaved: every repetition visits each route in turn.
+
 Every figure is wall clock around calls that end in a device synchronise (the
 device forms with stream = NULL synchronise the library stream before they
 return), the median of 5 repetitions after a warm-up; a repetition repeats
@@ -100,6 +118,185 @@ def host_tree(old, fr, leaves):
 
 
 APPEND_SIZES = (100, 256, 1000, 10000, 65536)
+PROVE_TREES = (10000, (1 << 20) + 12345)
+PROVE_N = 10000
+PROVE_SMALL = (16, 64, 256, 1024)
+
+
+class Hip:
+    """HIP events on a stream of the bench's own, from the runtime libedv.so uses."""
+
+    def __init__(self):
+        import ctypes
+        self.c = ctypes
+        for name in ("libamdhip64.so.7", "libamdhip64.so"):
+            try:
+                self.h = ctypes.CDLL(name)
+                break
+            except OSError:
+                continue
+        self.stream = ctypes.c_void_p()
+        assert self.h.hipStreamCreate(ctypes.byref(self.stream)) == 0
+        self.e0, self.e1 = ctypes.c_void_p(), ctypes.c_void_p()
+        assert self.h.hipEventCreate(ctypes.byref(self.e0)) == 0 and self.h.hipEventCreate(ctypes.byref(self.e1)) == 0
+
+    def timed(self, launch, inner):
+        """Seconds per launch: `inner` launches on the stream between two events."""
+        assert self.h.hipEventRecord(self.e0, self.stream) == 0
+        for _ in range(inner):
+            launch(self.stream.value)
+        assert self.h.hipEventRecord(self.e1, self.stream) == 0
+        assert self.h.hipEventSynchronize(self.e1) == 0
+        ms = self.c.c_float()
+        assert self.h.hipEventElapsedTime(self.c.byref(ms), self.e0, self.e1) == 0
+        return ms.value * 1e-3 / inner
+
+
+def timed_interleaved(routes, window, reps=5, hip=None):
+    """routes: name -> fn() (wall clock) or fn(stream) (HIP events, names starting with "a_" or "v_").
+    Every repetition visits each route in turn; the median over the repetitions per route."""
+    inner, out = {}, {k: [] for k in routes}
+
+    def once(name, k):
+        fn = routes[name]
+        if name[:2] in ("a_", "v_"):
+            return hip.timed(fn, k)
+        t0 = time.perf_counter()
+        for _ in range(k):
+            fn()
+        return (time.perf_counter() - t0) / k
+    for name in routes:
+        once(name, 1)   # warm-up
+        inner[name] = max(1, min(2000, int(window / max(once(name, 1), 1e-6))))
+    for _ in range(reps):
+        for name in routes:
+            out[name].append(once(name, inner[name]))
+    return {k: {"median_us": statistics.median(v) * 1e6, "min_us": min(v) * 1e6, "max_us": max(v) * 1e6,
+                "calls_per_repetition": inner[k], "repetitions": reps} for k, v in out.items()}
+
+
+def fold_efficiency(counts, lanes=64):
+    """Mean over waves of mean / max of the lanes' node hashes."""
+    c = np.asarray(counts, dtype=np.float64)
+    eff = [w.mean() / w.max() if w.max() else 1.0 for w in (c[lo:lo + lanes] for lo in range(0, len(c), lanes))]
+    return float(np.mean(eff))
+
+
+def prove_leg(args, rng):
+    """Batched proof generation against the host loop (module docstring)."""
+    from indy_plenum_amd.ledger import Ledger
+    hip = Hip()
+    res = {"window_s": args.window, "version": edv.version(), "proofs": PROVE_N, "rows": [], "crossover": []}
+    pc = lambda x: bin(int(x)).count("1")  # noqa: E731
+    v = merkle.MerkleVerifier()
+    for size in PROVE_TREES:
+        blob = np.arange(size, dtype=np.uint64).view(np.uint8).tobytes()
+        tree = merkle.CompactMerkleTree(hashStore=merkle.DeviceHashStore(args.device))
+        tree.extend([blob[8 * i:8 * i + 8] for i in range(size)], on_device=True, device=args.device)
+        store = tree.hashStore
+        d_leafs, d_nodes, leaves, _ = store.device_arrays()
+        leafs_h, nodes_h = np.frombuffer(bytes(store._leafs), np.uint8), np.frombuffer(bytes(store._nodes), np.uint8)
+        seqs = np.arange(size - PROVE_N + 1, size + 1, dtype=np.uint64)
+        sec = rng.integers(1, size + 1, PROVE_N).astype(np.uint64)
+        cases = {"merkle_info": (False, seqs - np.uint64(1), seqs),
+                 "inclusion": (False, rng.integers(0, size, PROVE_N).astype(np.uint64), np.full(PROVE_N, size, np.uint64)),
+                 "consistency": (True, (rng.integers(0, 2 ** 62, PROVE_N).astype(np.uint64) % sec) + np.uint64(1), sec)}
+        for name, (cons, a, b) in cases.items():
+            n = len(a)
+            pairs = list(zip(a.tolist(), b.tolist()))
+            hashes = [pc(y) - 1 + (pc(x) - 1 if cons else 0) for x, y in pairs]
+
+            def device_call(a, b):
+                off = (edv.merkle_consistency_offsets if cons else edv.merkle_inclusion_offsets)(a, b, leaves)
+                bufs = dict(a=dev(a), b=dev(b), off=dev(off), proofs=edv.DeviceBuffer(32 * max(1, int(off[-1]))),
+                            st=edv.DeviceBuffer(n), o1=edv.DeviceBuffer(32 * n), o2=edv.DeviceBuffer(32 * n),
+                            vst=edv.DeviceBuffer(n))
+                fn = edv.merkle_prove_consistency_device if cons else edv.merkle_prove_inclusion_device
+
+                def prove(stream):
+                    fn(d_leafs, d_nodes, leaves, bufs["a"].ptr, bufs["b"].ptr, bufs["off"].ptr, n, bufs["proofs"].ptr,
+                       bufs["st"].ptr, bufs["o1"].ptr, bufs["o2"].ptr, device=args.device, stream=stream)
+
+                def verify(stream):
+                    if cons:
+                        edv.merkle_verify_consistency_device(bufs["a"].ptr, bufs["b"].ptr, bufs["o1"].ptr, bufs["o2"].ptr,
+                                                             bufs["proofs"].ptr, bufs["off"].ptr, n, bufs["vst"].ptr,
+                                                             device=args.device, stream=stream)
+                    else:
+                        edv.merkle_verify_inclusion_device(bufs["a"].ptr, bufs["b"].ptr, bufs["o1"].ptr, bufs["proofs"].ptr,
+                                                           bufs["off"].ptr, n, bufs["vst"].ptr, d_leaf_hashes=bufs["o2"].ptr,
+                                                           device=args.device, stream=stream)
+                return bufs, off, prove, verify
+
+            bufs, off, prove, verify = device_call(a, b)
+            order = np.argsort([pc(y) for y in b.tolist()], kind="stable")
+            sbufs, _, prove_sorted, _ = device_call(a[order], b[order])
+            batch = tree.consistency_proof_batch if cons else tree.inclusion_proof_batch
+
+            def route_b():
+                return batch(pairs, on_device=True, device=args.device)
+
+            def route_c():
+                if cons:
+                    return edv.merkle_prove_consistency(leafs_h, nodes_h, leaves, a, b, device=args.device)
+                return edv.merkle_prove_inclusion(leafs_h, nodes_h, leaves, a, b, want_leaf_hashes=True, device=args.device)
+
+            def route_e():
+                return batch(pairs, on_device=False)
+
+            # results first: every route gives the host loop's bytes, and the verifier accepts them on the device
+            want = route_e()
+            prove(None)
+            verify(None)
+            assert (bufs["st"].download() == edv.PROOF_OK).all() and (bufs["vst"].download() == edv.PROOF_OK).all()
+            assert bufs["proofs"].download(32 * int(off[-1])).tobytes() == want.proofs.tobytes()
+            got_b, got_c = route_b(), route_c()
+            assert got_b.proofs.tobytes() == want.proofs.tobytes() == got_c[0].tobytes()
+            w1 = want.old_roots if cons else want.roots
+            assert bufs["o1"].download().tobytes() == w1.tobytes() == got_c[3].tobytes()
+            assert v.verify_proof_batch(got_b, on_device=True, device=args.device).ok.all()
+            t = timed_interleaved({"a_prove_dev": prove, "v_verify_dev": verify, "a_prove_dev_sorted_by_popcount": prove_sorted,
+                                   "b_device_hash_store": route_b, "c_prove_host_buffers": route_c,
+                                   "e_host_loop": route_e}, args.window, hip=hip)
+            row = {"tree": size, "case": name, "n": n, "entries_per_proof": int(off[-1]) / n,
+                   "node_hashes_per_proof": float(np.mean(hashes)), "lane_efficiency": fold_efficiency(hashes),
+                   "lane_efficiency_sorted": fold_efficiency(np.asarray(hashes)[order])}
+            row.update(t)
+            row["a_over_v"] = t["a_prove_dev"]["median_us"] / t["v_verify_dev"]["median_us"]
+            row["e_over_a"] = t["e_host_loop"]["median_us"] / t["a_prove_dev"]["median_us"]
+            row["sorted_wins"] = t["a_prove_dev_sorted_by_popcount"]["median_us"] < t["a_prove_dev"]["median_us"]
+            res["rows"].append(row)
+            print(json.dumps(row), flush=True)
+        # (b) against (e) at small sizes: the last k seqNos
+        for k in PROVE_SMALL:
+            some = list(range(size - k + 1, size + 1))
+            t = timed_interleaved({"b_device_hash_store": lambda: tree.merkle_info_batch(some, on_device=True,
+                                                                                         device=args.device),
+                                   "e_host_loop": lambda: tree.merkle_info_batch(some, on_device=False)}, args.window)
+            row = dict(t, tree=size, n=k)
+            row["b_beats_e"] = t["b_device_hash_store"]["median_us"] < t["e_host_loop"]["median_us"]
+            res["crossover"].append(row)
+            print(json.dumps(row), flush=True)
+        if size == PROVE_TREES[0]:
+            # base58 for the replies, pure Python, on a line of its own: not part of any route above
+            info = tree.merkle_info_batch(seqs.tolist(), on_device=True, device=args.device)
+            t0 = time.perf_counter()
+            for i, path in enumerate(info):
+                Ledger.hashToStr(info.roots[i].tobytes())
+                for h in path:
+                    Ledger.hashToStr(h)
+            res["base58_merkle_info_10000_replies_us"] = (time.perf_counter() - t0) * 1e6
+            print(json.dumps({"base58_us": res["base58_merkle_info_10000_replies_us"]}), flush=True)
+        store.reset()
+    cross = None
+    for k in sorted(PROVE_SMALL, reverse=True):
+        if all(r["b_beats_e"] for r in res["crossover"] if r["n"] == k):
+            cross = k
+        else:
+            break
+    res["min_device_prove_proofs"] = {"value": cross, "rule": "smallest measured n from which b < e on both trees, "
+                                      "at n and every larger n measured; null: at none"}
+    return res
 
 
 def lane_efficiency(old, n, lanes=64):
@@ -286,7 +483,7 @@ def verify_leg(args, rng):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=("extend", "append", "verify"), default="extend")
+    ap.add_argument("--leg", choices=("extend", "append", "verify", "prove"), default="extend")
     ap.add_argument("--out", default=None)
     ap.add_argument("--window", type=float, default=0.2)
     ap.add_argument("--device", type=int, default=0)
@@ -294,12 +491,13 @@ def main():
     if args.out is None:
         args.out = {"extend": os.path.join(ROOT, "profiles", "r07", "merkle_bench.json"),
                     "append": os.path.join(ROOT, "profiles", "r08", "merkle_append_bench.json"),
-                    "verify": os.path.join(ROOT, "profiles", "r09", "merkle_verify_bench.json")}[args.leg]
+                    "verify": os.path.join(ROOT, "profiles", "r09", "merkle_verify_bench.json"),
+                    "prove": os.path.join(ROOT, "profiles", "r10", "merkle_prove_bench.json")}[args.leg]
     if edv.device_count() < 1:
         sys.exit("bench_merkle needs a gfx950 GPU")
     rng = np.random.default_rng(0x6962)
-    if args.leg in ("append", "verify"):
-        res = append_leg(args, rng) if args.leg == "append" else verify_leg(args, rng)
+    if args.leg in ("append", "verify", "prove"):
+        res = {"append": append_leg, "verify": verify_leg, "prove": prove_leg}[args.leg](args, rng)
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump(res, f, indent=1)
