@@ -416,6 +416,84 @@ int edv_merkle_prove_consistency_dev(const uint8_t *d_leaf_store, const uint8_t 
                                      int device, void *stream);
 
 /*
+ * Auditing and repairing a hash store (row f-9): what nothing in the
+ * reference checks.  Its Ledger.recoverTree (ledger/ledger.py:70-114) trusts a
+ * store that has leaves, and CompactMerkleTree.verify_consistency
+ * (ledger/compact_merkle_tree.py) compares two counts; a store with one wrong
+ * byte passes both and yields wrong proofs from then on.  The store's
+ * invariant is local, so it is checked one lane per stored entry:
+ *   edv_merkle_audit_nodes   every node of the slice [node_lo, node_lo + count)
+ *               of the node store (0-based positions) is SHA-256(0x01 | left |
+ *               right) of its two children as they are stored: leaf-store
+ *               entries for a node of height 1, earlier node-store entries above
+ *   edv_merkle_audit_leaves  leaf-store entry leaf_lo + i is SHA-256(0x00 |
+ *               leaf i) for the n leaves at leaves / leaf_off (laid out as
+ *               msgs / msg_off everywhere else, readable 8 bytes past the end)
+ *   status      NULL, or one EDV_AUDIT_* byte per entry of the slice (0 never
+ *               means good)
+ *   summary     two words: the number of bad entries, and the lowest bad
+ *               position (0-based, in the store; UINT64_MAX: none).  A caller
+ *               needs these 16 bytes back, not one byte per node
+ * leaf_store / node_store are laid out as for edv_merkle_prove_*:
+ * store_leaves x 32 and (store_leaves - popcount(store_leaves)) x 32 bytes.  A
+ * node's children come before it, so a slice reads no position at or past its
+ * own end and no leaf the append of its last node had not seen; nothing at or
+ * past the counts is read.  A flipped bit in a node makes the node and its
+ * parent bad; one in a leaf hash makes its parent bad (and, with the leaf
+ * bytes given, the leaf).
+ * count / n are at most EDV_MERKLE_MAX_LEAVES per call: a larger store is
+ * audited in slices.  count = 0 / n = 0 are valid and write nothing but the
+ * host forms' initial summary.  EDV_E_ARG with nothing launched or written:
+ * count / n above EDV_MERKLE_MAX_LEAVES; store_leaves above 2^62; a slice that
+ * reaches past store_leaves - popcount(store_leaves) nodes / store_leaves
+ * leaves; NULL summary; with entries to read a NULL store, leaf_off or (unless
+ * every leaf is empty) leaves; host offsets that decrease.
+ * Device forms: async on `stream` (NULL = library stream, synchronised before
+ * returning), offsets absolute minus leaf_base; no context memory, so calls are
+ * ordered by their streams alone.  They ADD into the caller's d_summary, which
+ * the caller sets to {0, UINT64_MAX} first: several slices accumulate into one
+ * summary.  Alignment as edv_merkle_prove_*_dev: d_summary and d_leaf_off on 8
+ * bytes, both stores on 16, d_status and d_leaves any.
+ * Host forms: set summary to {0, UINT64_MAX} themselves, fill status with
+ * EDV_AUDIT_UNCHECKED, synchronous.  THEY COPY THE STORE TO THE DEVICE ON
+ * EVERY CALL: for nodes the prefix the slice reads (every node below its end
+ * and the leaves below the append of its last node), for leaves the slice's
+ * hashes and the leaf bytes.  They stage where the prove and verify host forms
+ * stage: counted in edv_context_memory out[2], cut by edv_trim, freed by
+ * edv_release; a ledger keeps its store on the device and uses the device forms.
+ *
+ * edv_merkle_extend_hashed is edv_merkle_extend from the n leaves' hashes
+ * instead of their bytes (a store loaded from disk, a catch-up peer that sends
+ * hashes): the same passes, the first of which reads its items as every later
+ * one does.  node_hashes (NULL: not wanted), new_hashes and root are
+ * byte-identical to edv_merkle_extend's on the leaves those hashes belong to;
+ * every limit, alignment rule and EDV_E_ARG case is edv_merkle_extend[_dev]'s,
+ * with leaf_hashes (n x 32 bytes, a hash buffer; NULL with n > 0 is
+ * EDV_E_ARG) in place of leaves / leaf_off.  It shares the extend's scratch
+ * and its ordering across streams.  From an empty tree over a store's leaf
+ * hashes it rebuilds the node store without the transaction log.
+ */
+#define EDV_AUDIT_UNCHECKED 0 /* never written by a kernel: what the host forms fill status with first */
+#define EDV_AUDIT_OK 1
+#define EDV_AUDIT_BAD 2
+int edv_merkle_audit_nodes(const uint8_t *leaf_store, const uint8_t *node_store, uint64_t store_leaves,
+                           uint64_t node_lo, uint64_t count, uint8_t *status, uint64_t summary[2], int device);
+int edv_merkle_audit_leaves(const uint8_t *leaf_store, uint64_t store_leaves, uint64_t leaf_lo,
+                            const uint8_t *leaves, const uint64_t *leaf_off, uint64_t n,
+                            uint8_t *status, uint64_t summary[2], int device);
+int edv_merkle_audit_nodes_dev(const uint8_t *d_leaf_store, const uint8_t *d_node_store, uint64_t store_leaves,
+                               uint64_t node_lo, uint64_t count, uint8_t *d_status, uint64_t *d_summary,
+                               int device, void *stream);
+int edv_merkle_audit_leaves_dev(const uint8_t *d_leaf_store, uint64_t store_leaves, uint64_t leaf_lo,
+                                const uint8_t *d_leaves, const uint64_t *d_leaf_off, uint64_t leaf_base, uint64_t n,
+                                uint8_t *d_status, uint64_t *d_summary, int device, void *stream);
+int edv_merkle_extend_hashed(uint64_t old_size, const uint8_t *old_hashes, const uint8_t *leaf_hashes, uint64_t n,
+                             uint8_t *node_hashes, uint8_t *new_hashes, uint8_t *root, int device);
+int edv_merkle_extend_hashed_dev(uint64_t old_size, const uint8_t *d_old_hashes, const uint8_t *d_leaf_hashes, uint64_t n,
+                                 uint8_t *d_node_hashes, uint8_t *d_new_hashes, uint8_t *d_root,
+                                 int device, void *stream);
+
+/*
  * Pipelined submission of device-resident batches (a continuous stream of
  * client batches, e.g. one per Node prod): enqueues the batch and returns
  * without waiting.  Consecutive submissions alternate between two internal

@@ -657,16 +657,20 @@ void hc_merkle_leaf_hash(const uint8_t* m, uint64_t mlen, int misalign, uint8_t*
 }
 // edv_merkle_extend's signature minus `device`: the kernels' passes and tiles,
 // lanes and levels run one after another (what __syncthreads() separates on
-// the device is a finished loop here).
-int hc_merkle_extend(uint64_t old_size, const uint8_t* old_hashes, const uint8_t* leaves, const uint64_t* off,
-                     uint64_t n, uint8_t* leaf_hashes, uint8_t* node_hashes, uint8_t* new_hashes, uint8_t* root) {
+// the device is a finished loop here).  leaf_in (row f-9): the n leaf hashes
+// instead of leaves / off, in a block of exactly 32 n bytes.
+static int hc_extend(uint64_t old_size, const uint8_t* old_hashes, const uint8_t* leaves, const uint64_t* off,
+                     const uint8_t* leaf_in, uint64_t n, uint8_t* leaf_hashes, uint8_t* node_hashes, uint8_t* new_hashes,
+                     uint8_t* root) {
   if (old_size > kMerkleMaxSize || n > kMerkleMaxSize || old_size + n > kMerkleMaxSize) return -1;
-  if ((old_size && !old_hashes) || !new_hashes || !root || (n && !off)) return -1;
-  for (uint64_t i = 0; i < n; i++)
+  if ((old_size && !old_hashes) || !new_hashes || !root || (n && !off && !leaf_in)) return -1;
+  for (uint64_t i = 0; i < n && !leaf_in; i++)
     if (off[i + 1] < off[i]) return -1;
   const uint64_t new_size = old_size + n;
   const uint64_t nodes = merkle_node_count(new_size) - merkle_node_count(old_size);
-  const uint64_t mbase = n ? off[0] : 0, mbytes = n ? off[n] - off[0] : 0;
+  const uint64_t mbase = n && !leaf_in ? off[0] : 0, mbytes = n && !leaf_in ? off[n] - off[0] : 0;
+  std::vector<uint32_t> inw(leaf_in ? 8 * n : 0);
+  if (leaf_in && n) memcpy(inw.data(), leaf_in, 32 * n);
   // the leaves keep their alignment relative to their offsets; 8 readable bytes past the end
   std::vector<uint32_t> lbuf((mbytes + 3 + 8) / 4 + 2, 0);
   uint8_t* lv = reinterpret_cast<uint8_t*>(lbuf.data()) + (mbase & 3);
@@ -688,7 +692,7 @@ int hc_merkle_extend(uint64_t old_size, const uint8_t* old_hashes, const uint8_t
         uint64_t g;
         if (!merkle_item_index(a, tile, j, &g)) continue;
         uint32_t H[8];
-        if (h0 == 0) {
+        if (h0 == 0 && !a.in) {
           const uint64_t i = g - old_size;
           merkle_leaf_hash(H, lv + (off[i] - mbase), off[i + 1] - off[i]);
         } else {
@@ -701,13 +705,23 @@ int hc_merkle_extend(uint64_t old_size, const uint8_t* old_hashes, const uint8_t
           merkle_level(a, tile, hl, j, lvl[(hl - 1) & 1], lvl[hl & 1]);
     }
     return 0;
-  });
+  }, leaf_in && n ? inw.data() : nullptr);
   merkle_finish(old_size, new_size, args.old_hashes, args.new_hashes, rootw.data());
   if (leaf_hashes && n) memcpy(leaf_hashes, leafw.data(), 32 * n);
   if (node_hashes && nodes) memcpy(node_hashes, nodew.data(), 32 * nodes);
   memcpy(new_hashes, neww.data(), 32 * size_t(popc64(new_size)));
   memcpy(root, rootw.data(), 32);
   return 0;
+}
+int hc_merkle_extend(uint64_t old_size, const uint8_t* old_hashes, const uint8_t* leaves, const uint64_t* off,
+                     uint64_t n, uint8_t* leaf_hashes, uint8_t* node_hashes, uint8_t* new_hashes, uint8_t* root) {
+  return hc_extend(old_size, old_hashes, leaves, off, nullptr, n, leaf_hashes, node_hashes, new_hashes, root);
+}
+// edv_merkle_extend_hashed's signature minus `device`
+int hc_merkle_extend_hashed(uint64_t old_size, const uint8_t* old_hashes, const uint8_t* leaf_hashes, uint64_t n,
+                            uint8_t* node_hashes, uint8_t* new_hashes, uint8_t* root) {
+  if (n && !leaf_hashes) return -1;
+  return hc_extend(old_size, old_hashes, nullptr, nullptr, leaf_hashes, n, nullptr, node_hashes, new_hashes, root);
 }
 // ---- the batched append (edv_merkle.h, row f-6)
 uint64_t hc_merkle_path_entries(uint64_t old_size, uint64_t n) { return merkle_path_entries(old_size, n); }
@@ -867,4 +881,78 @@ int hc_merkle_prove_consistency(const uint8_t* leaf_store, const uint8_t* node_s
   return hc_prove(leaf_store, node_store, store_leaves, first, second, proof_off, n, proofs, status, old_roots, new_roots,
                   merkle_prove_consistency_args, merkle_prove_consistency_lane);
 }
+
+// ---- auditing a stored tree (edv_merkle.h, row f-9)
+// 0: q is a position no store of at most 2^62 leaves has
+int hc_merkle_store_node_at(uint64_t q, uint64_t* s, int32_t* h) {
+  if (q >= merkle_node_count(kMerkleMaxSize)) return 0;
+  int hh;
+  merkle_store_node_at(q, s, &hh);
+  *h = hh;
+  return 1;
+}
+// The host C-ABI forms' signatures minus `device`: the kernels' lanes one after
+// another.  The stores go into heap blocks of exactly the sizes the counts give
+// (leaves: the slice's entries alone, as the host form stages them; the leaf
+// bytes 8 more, their alignment relative to their offsets kept), so a lane
+// reading one entry past the counts is ASan's to see.
+int hc_merkle_audit_nodes(const uint8_t* leaf_store, const uint8_t* node_store, uint64_t store_leaves, uint64_t node_lo,
+                          uint64_t count, uint8_t* status, uint64_t* summary) {
+  if (count > (uint64_t(1) << 22) || store_leaves > kMerkleMaxSize || !summary) return -1;
+  const uint64_t nodes = merkle_node_count(store_leaves);
+  if (node_lo > nodes || count > nodes - node_lo) return -1;
+  if (count && (!leaf_store || !node_store)) return -1;
+  merkle_audit_summary_init(summary);
+  if (!count) return 0;
+  std::vector<uint32_t> leafw(8 * store_leaves), nodew(8 * nodes);
+  memcpy(leafw.data(), leaf_store, 32 * store_leaves);
+  memcpy(nodew.data(), node_store, 32 * nodes);
+  std::vector<uint8_t> st(count, kAuditUnchecked);
+  const MerkleAuditNodes a = merkle_audit_nodes_args(leafw.data(), nodew.data(), node_lo, count, status ? st.data() : nullptr);
+  merkle_audit_run(a, count, node_lo, summary, merkle_audit_node_lane);
+  if (status) memcpy(status, st.data(), count);
+  return 0;
+}
+int hc_merkle_audit_leaves(const uint8_t* leaf_store, uint64_t store_leaves, uint64_t leaf_lo, const uint8_t* leaves,
+                           const uint64_t* leaf_off, uint64_t n, uint8_t* status, uint64_t* summary) {
+  if (n > (uint64_t(1) << 22) || store_leaves > kMerkleMaxSize || !summary) return -1;
+  if (leaf_lo > store_leaves || n > store_leaves - leaf_lo) return -1;
+  if (n && (!leaf_store || !leaf_off || !hc_offsets_ok(leaf_off, n))) return -1;
+  if (n && !leaves && leaf_off[n] != leaf_off[0]) return -1;
+  merkle_audit_summary_init(summary);
+  if (!n) return 0;
+  const uint64_t lbase = leaf_off[0], lbytes = leaf_off[n] - leaf_off[0];
+  std::vector<uint32_t> lbuf((lbytes + (lbase & 3) + 8 + 3) / 4), leafw(8 * n);
+  std::vector<uint64_t> loff(leaf_off, leaf_off + n + 1);
+  uint8_t* lv = reinterpret_cast<uint8_t*>(lbuf.data()) + (lbase & 3);
+  if (lbytes) memcpy(lv, leaves + lbase, lbytes);
+  memcpy(leafw.data(), leaf_store + 32 * leaf_lo, 32 * n);
+  std::vector<uint8_t> st(n, kAuditUnchecked);
+  const MerkleAuditLeaves a =
+      merkle_audit_leaves_args(leafw.data(), leaf_lo, leaf_lo, n, lv, loff.data(), lbase, status ? st.data() : nullptr);
+  merkle_audit_run(a, n, leaf_lo, summary, merkle_audit_leaf_lane);
+  if (status) memcpy(status, st.data(), n);
+  return 0;
+}
+// the host plan of the host forms, whole rows of kMerkleBufs = 20
+void hc_merkle_audit_nodes_needs(uint64_t node_lo, uint64_t count, uint64_t* out20, uint64_t* prefix2) {
+  const MerkleSizes s = merkle_audit_nodes_needs(node_lo, count);
+  memcpy(out20, s.data(), sizeof s);
+  prefix2[0] = prefix2[1] = 0;
+  if (count) {
+    const MerkleAuditPrefix p = merkle_audit_nodes_prefix(node_lo, count);
+    prefix2[0] = p.leaves;
+    prefix2[1] = p.nodes;
+  }
+}
+void hc_merkle_audit_leaves_needs(uint64_t n, uint64_t lbytes, uint64_t* out20) {
+  const MerkleSizes s = merkle_audit_leaves_needs(n, lbytes);
+  memcpy(out20, s.data(), sizeof s);
+}
+void hc_merkle_extend_hashed_needs(uint64_t old_size, uint64_t n, int host_form, int want_node, uint64_t* out20) {
+  const MerkleSizes s = merkle_extend_hashed_needs(old_size, n, host_form, want_node);
+  memcpy(out20, s.data(), sizeof s);
+}
+// out: kAuditUnchecked, kAuditOk, kAuditBad
+void hc_merkle_audit_consts(int32_t* out) { out[0] = kAuditUnchecked; out[1] = kAuditOk; out[2] = kAuditBad; }
 }

@@ -220,4 +220,49 @@ inline MerkleSizes merkle_prove_needs(uint64_t n, uint64_t prefix, uint64_t entr
   return s;
 }
 
+// ---- auditing a stored tree (row f-9).  The host forms stage in the buffers
+// the prove forms stage in (and the leaf bytes where the verify forms put
+// theirs): no buffer of their own, so edv_trim and edv_release cut and free
+// them as before.  mp_out: the summary's two words, then the statuses.
+constexpr uint64_t kAuditSummaryBytes = 16;
+// The store prefixes a node slice [node_lo, node_lo + count) reads, count > 0:
+// every node below its end, and the leaves below the append that wrote its
+// last node (merkle_node_children: children come before their parent).
+struct MerkleAuditPrefix {
+  uint64_t leaves, nodes;
+};
+inline MerkleAuditPrefix merkle_audit_nodes_prefix(uint64_t node_lo, uint64_t count) {
+  uint64_t s;
+  int h;
+  merkle_store_node_at(node_lo + count - 1, &s, &h);
+  return {s, node_lo + count};
+}
+inline MerkleSizes merkle_audit_nodes_needs(uint64_t node_lo, uint64_t count) {
+  MerkleSizes s = {};
+  if (!count) return s;
+  const MerkleAuditPrefix p = merkle_audit_nodes_prefix(node_lo, count);
+  s[mp_leaves] = 32 * p.leaves;
+  s[mp_nodes] = 32 * p.nodes;
+  s[mp_out] = kAuditSummaryBytes + count;
+  return s;
+}
+// ... and a leaf slice of n leaves, lbytes of them: the n stored hashes, the
+// leaf bytes, the n + 1 offsets.
+inline MerkleSizes merkle_audit_leaves_needs(uint64_t n, uint64_t lbytes) {
+  MerkleSizes s = {};
+  if (!n) return s;
+  s[mp_leaves] = 32 * n;
+  s[mv_leaves] = lbytes + kReadSlack;
+  s[mp_words] = 8 * (n + 1);
+  s[mp_out] = kAuditSummaryBytes + n;
+  return s;
+}
+// ... and an extend from n leaf hashes (host form): the extend's staging
+// without leaf bytes and offsets; mk_leafh holds the hashes that come in.
+inline MerkleSizes merkle_extend_hashed_needs(uint64_t old_size, uint64_t n, bool host_form, bool want_node) {
+  MerkleSizes s = merkle_extend_needs(old_size, n, 0, host_form, host_form, want_node, false, false);
+  s[mk_leaves] = s[mk_off] = 0;
+  return s;
+}
+
 }  // namespace edv

@@ -36,8 +36,8 @@ hipError_t launch_pack_bits_kernel(hipStream_t s, const uint8_t* acc, uint64_t n
 hipError_t launch_sha256_kernel(unsigned blocks, hipStream_t s, const uint8_t* msgs, const uint64_t* off,
                                 uint64_t msg_base, uint64_t n, uint32_t* out);
 // Merkle-tree extension (edv_merkle.hip; MerklePass: edv_merkle.h): one pass
-// over all its tiles (pass 0 hashes the leaves; no launch for a pass without
-// items), and the finish (kept entries of the new hashes, root)
+// over all its tiles (pass 0 hashes the leaves, or with a.in set reads their
+// hashes from it; no launch for a pass without items), and the finish (kept entries of the new hashes, root)
 struct MerklePass;
 hipError_t launch_merkle_pass_kernel(hipStream_t s, const MerklePass& a, const uint8_t* leaves, const uint64_t* off,
                                      uint64_t leaf_base);
@@ -60,5 +60,13 @@ struct MerkleProveInclusion;
 struct MerkleProveConsistency;
 hipError_t launch_merkle_prove_inclusion_kernel(hipStream_t s, const MerkleProveInclusion& a);
 hipError_t launch_merkle_prove_consistency_kernel(hipStream_t s, const MerkleProveConsistency& a);
+// auditing a stored tree (MerkleAuditNodes / MerkleAuditLeaves: edv_merkle.h),
+// one lane per stored entry; summary: two words the launch adds into (bad
+// entries, lowest bad position), set to {0, UINT64_MAX} by whoever owns them;
+// no launch for an empty slice
+struct MerkleAuditNodes;
+struct MerkleAuditLeaves;
+hipError_t launch_merkle_audit_nodes_kernel(hipStream_t s, const MerkleAuditNodes& a, uint64_t* summary);
+hipError_t launch_merkle_audit_leaves_kernel(hipStream_t s, const MerkleAuditLeaves& a, uint64_t* summary);
 
 }  // namespace edv

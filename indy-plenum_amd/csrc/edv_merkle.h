@@ -4,7 +4,8 @@
 // audit paths and consistency proofs, a batch at a time (row f-7, at the end of
 // this file; ledger/merkle_verifier.py MerkleVerifier), and the making of them
 // from the stored hashes (row f-8, after it; CompactMerkleTree.inclusion_proof
-// / consistency_proof / merkle_tree_hash(0, n)).
+// / consistency_proof / merkle_tree_hash(0, n)), and the auditing of those
+// stored hashes, entry by entry (row f-9, at the very end).
 //
 // Replaces, per batch of transactions:
 //   ledger/ledger.py:145-148              Ledger._addToTree (one append per txn)
@@ -301,9 +302,12 @@ inline MerklePass merkle_pass_args(uint64_t old_size, uint64_t new_size, const v
   return {old_size, new_size, 0, static_cast<const uint32_t*>(old_hashes), nullptr, H(leaf_out), H(node_out),
           H(new_hashes), nullptr};
 }
+// leaf_in (row f-9, extend from hashes): the n leaf hashes instead of leaf
+// bytes; pass 0 then loads its items from them, as every later pass loads its.
 template <class F>
-inline auto merkle_for_each_pass(uint64_t old_size, uint64_t new_size, uint32_t* roots_base, MerklePass& a, F run_pass) {
-  a.in = nullptr;
+inline auto merkle_for_each_pass(uint64_t old_size, uint64_t new_size, uint32_t* roots_base, MerklePass& a, F run_pass,
+                                 const uint32_t* leaf_in = nullptr) {
+  a.in = leaf_in;
   for (int h0 = 0; merkle_pass_runs(old_size, new_size, h0); h0 += kMerkleLogT) {
     const uint64_t next_items =
         merkle_pass_runs(old_size, new_size, h0 + kMerkleLogT) ? merkle_pass_items(old_size, new_size, h0 + kMerkleLogT) : 0;
@@ -897,6 +901,125 @@ EDV_HD void merkle_prove_consistency_lane(const MerkleProveConsistency& a, uint6
   if (a.old_roots) {
     if (ok) merkle_fold_store(root, a.leaf_store, a.node_store, first, 64, nullptr, true);
     merkle_store_hash_or_zero(a.old_roots + 8 * i, root, ok);
+  }
+}
+
+// ---- auditing a stored tree (row f-9: what nothing in ledger/ledger.py:70-114
+// recoverTree or compact_merkle_tree.py verify_consistency checks, one lane per
+// stored entry).  The store's invariant is local: the node at position q is
+// SHA-256(0x01 | left | right) of two entries that are stored too, and leaf
+// hash k is SHA-256(0x00 | leaf k).  One status byte per entry; 0 is never
+// written by a lane.
+constexpr uint8_t kAuditUnchecked = 0;  // EDV_AUDIT_* of include/edv.h
+constexpr uint8_t kAuditOk = 1;
+constexpr uint8_t kAuditBad = 2;
+
+// The inverse of merkle_store_pos: the append that wrote 0-based node-store
+// position q, as the 1-based leaf count s, and the node's height h in
+// 1 .. ctz(s) (its block is (s >> h) - 1).  With f = merkle_node_count, s is
+// the smallest value with f(s) > q and h = q - f(s - 1) + 1.  f never falls
+// (f(s + 1) - f(s) = ctz(s + 1)) and s - 63 <= f(s) <= s - 1 for s <= 2^62, so
+// s lies in [q + 2, q + 64]: six halvings.  Exact for q < merkle_node_count(2^62).
+EDV_HD void merkle_store_node_at(uint64_t q, uint64_t* s, int* h) {
+  uint64_t lo = q + 2, hi = q + 64;
+#pragma unroll 1
+  while (lo < hi) {
+    const uint64_t mid = lo + ((hi - lo) >> 1);
+    if (merkle_node_count(mid) > q)
+      hi = mid;
+    else
+      lo = mid + 1;
+  }
+  *s = lo;
+  *h = int(q - merkle_node_count(lo - 1)) + 1;
+}
+// The two children of block k at height h >= 1: leaf-store entries 2k and
+// 2k + 1 (h = 1, *leaves), else 0-based node-store positions.  Both are below
+// the node's own append: a node at position q reads no node at or past q and
+// no leaf at or past its s.
+EDV_HD void merkle_node_children(int h, uint64_t k, bool* leaves, uint64_t* left, uint64_t* right) {
+  *leaves = h == 1;
+  if (h == 1) {
+    *left = 2 * k;
+    *right = 2 * k + 1;
+  } else {
+    *left = merkle_store_pos(h - 1, 2 * k) - 1;
+    *right = merkle_store_pos(h - 1, 2 * k + 1) - 1;
+  }
+}
+
+// One slice of the node store: positions [node_lo, node_lo + count), 0-based.
+struct MerkleAuditNodes {
+  const uint32_t* leaf_store;
+  const uint32_t* node_store;
+  uint64_t node_lo, count;
+  uint8_t* status;  // one byte per position of the slice, or null
+};
+inline MerkleAuditNodes merkle_audit_nodes_args(const void* leaf_store, const void* node_store, uint64_t node_lo,
+                                                uint64_t count, uint8_t* status) {
+  return {static_cast<const uint32_t*>(leaf_store), static_cast<const uint32_t*>(node_store), node_lo, count, status};
+}
+// Lane i < a.count: is the node at position node_lo + i not the hash of its stored children?
+EDV_HD bool merkle_audit_node_lane(const MerkleAuditNodes& a, uint64_t i) {
+  const uint64_t q = a.node_lo + i;
+  uint64_t s, left, right;
+  int h;
+  bool leaves;
+  merkle_store_node_at(q, &s, &h);
+  merkle_node_children(h, (s >> h) - 1, &leaves, &left, &right);
+  const uint32_t* from = leaves ? a.leaf_store : a.node_store;
+  uint32_t l[8], r[8], H[8], stored[8];
+  merkle_load_hash(l, from + 8 * left);
+  merkle_load_hash(r, from + 8 * right);
+  merkle_load_hash(stored, a.node_store + 8 * q);
+  merkle_node_hash(H, l, r);
+  const bool bad = !merkle_hash_equal(H, stored);
+  if (a.status) a.status[i] = bad ? kAuditBad : kAuditOk;
+  return bad;
+}
+
+// One slice of the leaf store against the leaves' bytes: leaf i of the call is
+// bytes [leaf_off[i], leaf_off[i + 1]) - leaf_base of `leaves` (the verify
+// kernel's layout and rules: any alignment, readable 8 bytes past the end) and
+// must hash to leaf-store entry leaf_lo + i, which is at 8 (leaf_lo + i -
+// store_base) of leaf_store (store_base: the entry leaf_store points at; 0 for
+// a whole store, leaf_lo where only the slice is at hand).
+struct MerkleAuditLeaves {
+  const uint32_t* leaf_store;
+  uint64_t store_base, leaf_lo, n;
+  const uint8_t* leaves;
+  const uint64_t* leaf_off;
+  uint64_t leaf_base;
+  uint8_t* status;  // one byte per leaf of the slice, or null
+};
+inline MerkleAuditLeaves merkle_audit_leaves_args(const void* leaf_store, uint64_t store_base, uint64_t leaf_lo,
+                                                  uint64_t n, const uint8_t* leaves, const uint64_t* leaf_off,
+                                                  uint64_t leaf_base, uint8_t* status) {
+  return {static_cast<const uint32_t*>(leaf_store), store_base, leaf_lo, n, leaves, leaf_off, leaf_base, status};
+}
+EDV_HD bool merkle_audit_leaf_lane(const MerkleAuditLeaves& a, uint64_t i) {
+  const uint64_t o0 = a.leaf_off[i] - a.leaf_base, o1 = a.leaf_off[i + 1] - a.leaf_base;
+  uint32_t H[8], stored[8];
+  merkle_leaf_hash(H, a.leaves + o0, o1 - o0);
+  merkle_load_hash(stored, a.leaf_store + 8 * (a.leaf_lo + i - a.store_base));
+  const bool bad = !merkle_hash_equal(H, stored);
+  if (a.status) a.status[i] = bad ? kAuditBad : kAuditOk;
+  return bad;
+}
+// A launch's summary: the number of bad entries and the lowest bad position
+// (0-based; UINT64_MAX: none).  Empty: {0, UINT64_MAX}; adding is commutative,
+// so slices and workgroups accumulate into one in any order.
+EDV_HD void merkle_audit_summary_init(uint64_t summary[2]) {
+  summary[0] = 0;
+  summary[1] = ~uint64_t(0);
+}
+// (host side) a slice's lanes one after another into summary
+template <class Args, class Lane>
+inline void merkle_audit_run(const Args& a, uint64_t count, uint64_t first_pos, uint64_t summary[2], Lane lane) {
+  for (uint64_t i = 0; i < count; i++) {
+    if (!lane(a, i)) continue;
+    summary[0]++;
+    if (first_pos + i < summary[1]) summary[1] = first_pos + i;
   }
 }
 

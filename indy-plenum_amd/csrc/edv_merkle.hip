@@ -94,6 +94,37 @@ __global__ __launch_bounds__(kMerkleAppendLanes) void edv_merkle_prove_consisten
   if (i < a.n) merkle_prove_consistency_lane(a, i);
 }
 
+// Row f-9: one lane checks one stored entry (merkle_audit_node_lane: two
+// 32-byte child loads, the stored node, two compressions; merkle_audit_leaf_lane:
+// the leaf's blocks and one stored hash).  The same shape once more: no LDS, no
+// lane reads what another wrote, 64-lane workgroups.  A node's children are
+// gathers above height 1 (neighbouring positions do not have neighbouring
+// children); the plain form is kept, see DESIGN.md section 3b row f-9.  The
+// summary is reduced in the workgroup first: a workgroup is one wave of 64
+// lanes in position order, so the ballot of the bad lanes gives the count and,
+// by its lowest set bit, the lowest bad position; lane 0 of a workgroup that
+// found something adds them to the caller's two words.  Every lane reaches the
+// ballot.
+static_assert(kMerkleAppendLanes == 64, "the audit summary takes a workgroup to be one wave of 64 lanes");
+__device__ void merkle_audit_reduce(bool bad, uint64_t first_pos, uint64_t* summary) {
+  const unsigned long long mask = __ballot(bad);
+  if (threadIdx.x == 0 && mask != 0) {
+    unsigned long long* s = reinterpret_cast<unsigned long long*>(summary);
+    atomicAdd(s, static_cast<unsigned long long>(__popcll(mask)));
+    atomicMin(s + 1, static_cast<unsigned long long>(first_pos + uint64_t(__ffsll(mask) - 1)));
+  }
+}
+__global__ __launch_bounds__(kMerkleAppendLanes) void edv_merkle_audit_nodes_kernel(MerkleAuditNodes a, uint64_t* summary) {
+  const uint64_t i0 = uint64_t(blockIdx.x) * kMerkleAppendLanes, i = i0 + threadIdx.x;
+  const bool bad = i < a.count && merkle_audit_node_lane(a, i);
+  merkle_audit_reduce(bad, a.node_lo + i0, summary);
+}
+__global__ __launch_bounds__(kMerkleAppendLanes) void edv_merkle_audit_leaves_kernel(MerkleAuditLeaves a, uint64_t* summary) {
+  const uint64_t i0 = uint64_t(blockIdx.x) * kMerkleAppendLanes, i = i0 + threadIdx.x;
+  const bool bad = i < a.n && merkle_audit_leaf_lane(a, i);
+  merkle_audit_reduce(bad, a.leaf_lo + i0, summary);
+}
+
 }  // namespace
 
 namespace edv {
@@ -103,7 +134,8 @@ hipError_t launch_merkle_pass_kernel(hipStream_t s, const MerklePass& a, const u
   const uint64_t tiles = merkle_pass_tiles(a.old_size, a.new_size, a.h0);
   if (tiles == 0) return hipSuccess;
   const uint64_t tile0 = merkle_pass_first_tile(a.old_size, a.h0);
-  if (a.h0 == 0)
+  // a.in at height 0: the caller's leaf hashes (extend from hashes, row f-9)
+  if (a.h0 == 0 && !a.in)
     edv_merkle_pass_kernel<true><<<dim3(unsigned(tiles)), dim3(kMerkleT), 0, s>>>(a, tile0, leaves, off, leaf_base);
   else
     edv_merkle_pass_kernel<false><<<dim3(unsigned(tiles)), dim3(kMerkleT), 0, s>>>(a, tile0, nullptr, nullptr, 0);
@@ -151,6 +183,20 @@ hipError_t launch_merkle_prove_consistency_kernel(hipStream_t s, const MerklePro
   if (a.n == 0) return hipSuccess;
   const uint64_t blocks = (a.n + kMerkleAppendLanes - 1) / kMerkleAppendLanes;
   edv_merkle_prove_consistency_kernel<<<dim3(unsigned(blocks)), dim3(kMerkleAppendLanes), 0, s>>>(a);
+  return hipGetLastError();
+}
+
+hipError_t launch_merkle_audit_nodes_kernel(hipStream_t s, const MerkleAuditNodes& a, uint64_t* summary) {
+  if (a.count == 0) return hipSuccess;
+  const uint64_t blocks = (a.count + kMerkleAppendLanes - 1) / kMerkleAppendLanes;
+  edv_merkle_audit_nodes_kernel<<<dim3(unsigned(blocks)), dim3(kMerkleAppendLanes), 0, s>>>(a, summary);
+  return hipGetLastError();
+}
+
+hipError_t launch_merkle_audit_leaves_kernel(hipStream_t s, const MerkleAuditLeaves& a, uint64_t* summary) {
+  if (a.n == 0) return hipSuccess;
+  const uint64_t blocks = (a.n + kMerkleAppendLanes - 1) / kMerkleAppendLanes;
+  edv_merkle_audit_leaves_kernel<<<dim3(unsigned(blocks)), dim3(kMerkleAppendLanes), 0, s>>>(a, summary);
   return hipGetLastError();
 }
 

@@ -1310,10 +1310,13 @@ int run_digest_shard(DevCtx& c, const uint8_t* msgs, const uint64_t* off, uint64
 // d_aroots / d_paths (either may be null): the per-leaf roots and packed audit
 // paths of the batched append, by one more kernel after the finish.  Where it
 // reads leaf or node hashes that d_leafh / d_nodeh do not take, they go to
-// mk_fleafh / mk_fnodeh, scratch under the same event.  Caller holds c.mu.
+// mk_fleafh / mk_fnodeh, scratch under the same event.  d_leaf_in (row f-9):
+// the n leaf hashes instead of d_leaves / d_off; pass 0 reads them.  Caller
+// holds c.mu.
 int launch_merkle(DevCtx& c, uint64_t old_size, const uint8_t* d_old, const uint8_t* d_leaves, const uint64_t* d_off,
                   uint64_t leaf_base, uint64_t n, uint8_t* d_leafh, uint8_t* d_nodeh, uint8_t* d_new, uint8_t* d_root,
-                  hipStream_t s, uint8_t* d_aroots = nullptr, uint8_t* d_paths = nullptr) {
+                  hipStream_t s, uint8_t* d_aroots = nullptr, uint8_t* d_paths = nullptr,
+                  const uint8_t* d_leaf_in = nullptr) {
   MerkleBufs& m = c.mk;
   const uint64_t new_size = old_size + n;
   if (!m.done) HIPOK(hipEventCreateWithFlags(&m.done, hipEventDisableTiming), "event");
@@ -1325,7 +1328,8 @@ int launch_merkle(DevCtx& c, uint64_t old_size, const uint8_t* d_old, const uint
   if (need[mk_fnodeh]) d_nodeh = m.at(mk_fnodeh);
   MerklePass a = merkle_pass_args(old_size, new_size, d_old, d_leafh, d_nodeh, d_new);
   HIPOK(merkle_for_each_pass(old_size, new_size, m.at<uint32_t>(mk_roots), a,
-                             [&](const MerklePass& p) { return launch_merkle_pass_kernel(s, p, d_leaves, d_off, leaf_base); }),
+                             [&](const MerklePass& p) { return launch_merkle_pass_kernel(s, p, d_leaves, d_off, leaf_base); },
+                             reinterpret_cast<const uint32_t*>(d_leaf_in)),
         "merkle pass launch");
   HIPOK(launch_merkle_finish_kernel(s, old_size, new_size, a.old_hashes, a.new_hashes,
                                     reinterpret_cast<uint32_t*>(d_root)),
@@ -1491,6 +1495,83 @@ int run_prove_host(DevCtx& c, const uint8_t* leaf_store, const uint8_t* node_sto
   HIPOK(hipMemcpyAsync(status, d_status, n, hipMemcpyDeviceToHost, s), "d2h proof status");
   if (out1) HIPOK(hipMemcpyAsync(out1, d_1, 32 * n, hipMemcpyDeviceToHost, s), "d2h roots");
   if (out2) HIPOK(hipMemcpyAsync(out2, d_2, 32 * n, hipMemcpyDeviceToHost, s), "d2h roots");
+  HIPOK(hipStreamSynchronize(s), "stream sync");
+  return 0;
+}
+
+// ---- auditing a stored tree (edv_merkle.h, row f-9).  The host forms: the
+// store prefix the slice reads (nodes) or the slice of stored hashes with the
+// leaf bytes and offsets (leaves) staged where the prove and verify forms stage
+// (merkle_audit_*_needs), the summary set to empty on the device, the device
+// forms' launch on the library stream, the summary and the statuses (if asked
+// for) copied back, synchronous.  Caller holds c.mu and has checked the
+// arguments; count / n > 0.
+int finish_audit_host(DevCtx& c, uint64_t n, uint8_t* status, uint64_t summary[2]) {
+  uint8_t* d_out = c.mk.at(mp_out);
+  HIPOK(hipMemcpyAsync(summary, d_out, kAuditSummaryBytes, hipMemcpyDeviceToHost, c.stream), "d2h audit summary");
+  if (status) HIPOK(hipMemcpyAsync(status, d_out + kAuditSummaryBytes, n, hipMemcpyDeviceToHost, c.stream), "d2h audit status");
+  HIPOK(hipStreamSynchronize(c.stream), "stream sync");
+  return 0;
+}
+int run_audit_nodes_host(DevCtx& c, const uint8_t* leaf_store, const uint8_t* node_store, uint64_t node_lo,
+                         uint64_t count, uint8_t* status, uint64_t summary[2]) {
+  MerkleBufs& m = c.mk;
+  const hipStream_t s = c.stream;
+  if (const int err = m.ensure(merkle_audit_nodes_needs(node_lo, count))) return err;
+  const MerkleAuditPrefix p = merkle_audit_nodes_prefix(node_lo, count);
+  uint64_t empty[2];
+  merkle_audit_summary_init(empty);
+  uint8_t* d_out = m.at(mp_out);
+  HIPOK(hipMemcpyAsync(m.at(mp_leaves), leaf_store, 32 * p.leaves, hipMemcpyHostToDevice, s), "h2d leaf store");
+  HIPOK(hipMemcpyAsync(m.at(mp_nodes), node_store, 32 * p.nodes, hipMemcpyHostToDevice, s), "h2d node store");
+  HIPOK(hipMemcpyAsync(d_out, empty, kAuditSummaryBytes, hipMemcpyHostToDevice, s), "h2d audit summary");
+  HIPOK(launch_merkle_audit_nodes_kernel(s, merkle_audit_nodes_args(m.at(mp_leaves), m.at(mp_nodes), node_lo, count,
+                                                                    status ? d_out + kAuditSummaryBytes : nullptr),
+                                         reinterpret_cast<uint64_t*>(d_out)),
+        "merkle audit launch");
+  return finish_audit_host(c, count, status, summary);
+}
+int run_audit_leaves_host(DevCtx& c, const uint8_t* leaf_store, uint64_t leaf_lo, const uint8_t* leaves,
+                          const uint64_t* leaf_off, uint64_t n, uint8_t* status, uint64_t summary[2]) {
+  MerkleBufs& m = c.mk;
+  const hipStream_t s = c.stream;
+  const uint64_t lbytes = leaf_off[n] - leaf_off[0];
+  if (const int err = m.ensure(merkle_audit_leaves_needs(n, lbytes))) return err;
+  uint64_t empty[2];
+  merkle_audit_summary_init(empty);
+  uint8_t* d_out = m.at(mp_out);
+  HIPOK(hipMemcpyAsync(m.at(mp_leaves), leaf_store + 32 * leaf_lo, 32 * n, hipMemcpyHostToDevice, s), "h2d leaf store");
+  if (lbytes) HIPOK(hipMemcpyAsync(m.at(mv_leaves), leaves + leaf_off[0], lbytes, hipMemcpyHostToDevice, s), "h2d leaves");
+  HIPOK(hipMemcpyAsync(m.at(mp_words), leaf_off, 8 * (n + 1), hipMemcpyHostToDevice, s), "h2d leaf_off");
+  HIPOK(hipMemcpyAsync(d_out, empty, kAuditSummaryBytes, hipMemcpyHostToDevice, s), "h2d audit summary");
+  // the staged slice starts at entry leaf_lo of the store, the staged bytes at leaf_off[0]
+  HIPOK(launch_merkle_audit_leaves_kernel(
+            s, merkle_audit_leaves_args(m.at(mp_leaves), leaf_lo, leaf_lo, n, m.at(mv_leaves), m.at<uint64_t>(mp_words),
+                                        leaf_off[0], status ? d_out + kAuditSummaryBytes : nullptr),
+            reinterpret_cast<uint64_t*>(d_out)),
+        "merkle audit launch");
+  return finish_audit_host(c, n, status, summary);
+}
+// The host form of the extend from hashes: run_merkle_host without leaf bytes;
+// the n hashes go up into mk_leafh and pass 0 reads them there.
+int run_merkle_hashed_host(DevCtx& c, uint64_t old_size, const uint8_t* old_hashes, const uint8_t* leaf_hashes,
+                           uint64_t n, uint8_t* node_hashes, uint8_t* new_hashes, uint8_t* root) {
+  MerkleBufs& m = c.mk;
+  const uint64_t new_size = old_size + n, nodes = merkle_node_count(new_size) - merkle_node_count(old_size);
+  const uint64_t nold = uint64_t(popc64(old_size)), nnew = uint64_t(popc64(new_size));
+  const MerkleSizes need = merkle_extend_hashed_needs(old_size, n, true, node_hashes);
+  if (const int err = m.ensure(need)) return err;
+  const hipStream_t s = c.stream;
+  uint8_t *d_old = m.at(mk_hashes), *d_new = d_old + 32 * kMerkleMaxHashes, *d_root = d_new + 32 * kMerkleMaxHashes;
+  if (n) HIPOK(hipMemcpyAsync(m.at(mk_leafh), leaf_hashes, 32 * n, hipMemcpyHostToDevice, s), "h2d leaf hashes");
+  if (nold) HIPOK(hipMemcpyAsync(d_old, old_hashes, 32 * nold, hipMemcpyHostToDevice, s), "h2d old hashes");
+  uint8_t* d_nodeh = m.at(mk_nodeh, need);
+  if (const int err = launch_merkle(c, old_size, d_old, nullptr, nullptr, 0, n, nullptr, d_nodeh, d_new, d_root, s,
+                                    nullptr, nullptr, n ? m.at(mk_leafh) : nullptr))
+    return err;
+  if (node_hashes && d_nodeh) HIPOK(hipMemcpyAsync(node_hashes, d_nodeh, 32 * nodes, hipMemcpyDeviceToHost, s), "d2h node hashes");
+  if (nnew) HIPOK(hipMemcpyAsync(new_hashes, d_new, 32 * nnew, hipMemcpyDeviceToHost, s), "d2h new hashes");
+  HIPOK(hipMemcpyAsync(root, d_root, 32, hipMemcpyDeviceToHost, s), "d2h root");
   HIPOK(hipStreamSynchronize(s), "stream sync");
   return 0;
 }
@@ -2558,6 +2639,127 @@ int edv_merkle_prove_consistency_dev(const uint8_t* d_leaf_store, const uint8_t*
                                      uint8_t* d_old_roots, uint8_t* d_new_roots, int device, void* stream) {
   return prove_dev(true, d_leaf_store, d_node_store, store_leaves, d_first, d_second, d_proof_off, proof_base, n, d_proofs,
                          d_status, d_old_roots, d_new_roots, device, stream);
+}
+
+// Auditing a stored tree (row f-9).  What both forms of a call check before
+// anything is launched or written: the slice [lo, lo + count) against `total`
+// entries (the store's nodes or leaves), the summary, the stores a non-empty
+// slice reads.
+static int check_audit_args(uint64_t store_leaves, uint64_t lo, uint64_t count, uint64_t total, const void* summary,
+                            std::initializer_list<const void*> read) {
+  if (count > EDV_MERKLE_MAX_LEAVES) return set_err(EDV_E_ARG, "merkle audit: more than EDV_MERKLE_MAX_LEAVES entries");
+  if (store_leaves > kMerkleMaxSize) return set_err(EDV_E_ARG, "merkle audit: store_leaves above 2^62");
+  if (lo > total || count > total - lo) return set_err(EDV_E_ARG, "merkle audit: the slice reaches past the store");
+  if (!summary) return set_err(EDV_E_ARG, "merkle audit: null summary");
+  if (count)
+    for (const void* p : read)
+      if (!p) return set_err(EDV_E_ARG, "merkle audit: null pointer");
+  return 0;
+}
+
+int edv_merkle_audit_nodes(const uint8_t* leaf_store, const uint8_t* node_store, uint64_t store_leaves, uint64_t node_lo,
+                           uint64_t count, uint8_t* status, uint64_t summary[2], int device) {
+  g_err.clear();
+  if (const int err = check_audit_args(store_leaves, node_lo, count,
+                                       store_leaves <= kMerkleMaxSize ? merkle_node_count(store_leaves) : 0, summary,
+                                       {leaf_store, node_store}))
+    return err;
+  merkle_audit_summary_init(summary);
+  if (!count) return 0;
+  CtxLock cl(device);
+  if (cl.err) return cl.err;
+  if (status) memset(status, EDV_AUDIT_UNCHECKED, count);  // a call that fails part-way leaves nothing marked good
+  return run_audit_nodes_host(*cl.c, leaf_store, node_store, node_lo, count, status, summary);
+}
+
+int edv_merkle_audit_leaves(const uint8_t* leaf_store, uint64_t store_leaves, uint64_t leaf_lo, const uint8_t* leaves,
+                            const uint64_t* leaf_off, uint64_t n, uint8_t* status, uint64_t summary[2], int device) {
+  g_err.clear();
+  int err;
+  if ((err = check_audit_args(store_leaves, leaf_lo, n, store_leaves, summary, {leaf_store, leaf_off}))) return err;
+  if (n) {
+    if ((err = check_offsets(leaf_off, n))) return err;
+    if (!leaves && leaf_off[n] != leaf_off[0]) return set_err(EDV_E_ARG, "merkle audit: null leaves");
+  }
+  merkle_audit_summary_init(summary);
+  if (!n) return 0;
+  CtxLock cl(device);
+  if (cl.err) return cl.err;
+  if (status) memset(status, EDV_AUDIT_UNCHECKED, n);
+  return run_audit_leaves_host(*cl.c, leaf_store, leaf_lo, leaves, leaf_off, n, status, summary);
+}
+
+int edv_merkle_audit_nodes_dev(const uint8_t* d_leaf_store, const uint8_t* d_node_store, uint64_t store_leaves,
+                               uint64_t node_lo, uint64_t count, uint8_t* d_status, uint64_t* d_summary, int device,
+                               void* stream) {
+  g_err.clear();
+  int err;
+  if ((err = check_audit_args(store_leaves, node_lo, count,
+                              store_leaves <= kMerkleMaxSize ? merkle_node_count(store_leaves) : 0, d_summary,
+                              {d_leaf_store, d_node_store})))
+    return err;
+  // the lanes read every hash as two 16-byte vectors; the summary's words are 64-bit atomics' targets
+  if ((err = check_proof_align({d_summary}, {d_leaf_store, d_node_store}))) return err;
+  if (!count) return 0;
+  CtxLock cl(device);
+  if (cl.err) return cl.err;
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : cl.c->stream;
+  HIPOK(launch_merkle_audit_nodes_kernel(s, merkle_audit_nodes_args(d_leaf_store, d_node_store, node_lo, count, d_status),
+                                         d_summary),
+        "merkle audit launch");
+  if (!stream) HIPOK(hipStreamSynchronize(s), "stream sync");
+  return 0;
+}
+
+int edv_merkle_audit_leaves_dev(const uint8_t* d_leaf_store, uint64_t store_leaves, uint64_t leaf_lo,
+                                const uint8_t* d_leaves, const uint64_t* d_leaf_off, uint64_t leaf_base, uint64_t n,
+                                uint8_t* d_status, uint64_t* d_summary, int device, void* stream) {
+  g_err.clear();
+  int err;
+  if ((err = check_audit_args(store_leaves, leaf_lo, n, store_leaves, d_summary, {d_leaf_store, d_leaves, d_leaf_off})))
+    return err;
+  if ((err = check_proof_align({d_summary, d_leaf_off}, {d_leaf_store}))) return err;
+  if (!n) return 0;
+  CtxLock cl(device);
+  if (cl.err) return cl.err;
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : cl.c->stream;
+  HIPOK(launch_merkle_audit_leaves_kernel(
+            s, merkle_audit_leaves_args(d_leaf_store, 0, leaf_lo, n, d_leaves, d_leaf_off, leaf_base, d_status), d_summary),
+        "merkle audit launch");
+  if (!stream) HIPOK(hipStreamSynchronize(s), "stream sync");
+  return 0;
+}
+
+// Extend from leaf hashes (row f-9): the extend's checks, passes and scratch; pass 0 reads hashes.
+int edv_merkle_extend_hashed(uint64_t old_size, const uint8_t* old_hashes, const uint8_t* leaf_hashes, uint64_t n,
+                             uint8_t* node_hashes, uint8_t* new_hashes, uint8_t* root, int device) {
+  g_err.clear();
+  int err;
+  if ((err = check_append_args(old_size, n, old_hashes, new_hashes, root, ""))) return err;
+  if (n && !leaf_hashes) return set_err(EDV_E_ARG, "merkle: null leaf_hashes");
+  CtxLock cl(device);
+  if (cl.err) return cl.err;
+  return run_merkle_hashed_host(*cl.c, old_size, old_hashes, leaf_hashes, n, node_hashes, new_hashes, root);
+}
+
+int edv_merkle_extend_hashed_dev(uint64_t old_size, const uint8_t* d_old_hashes, const uint8_t* d_leaf_hashes, uint64_t n,
+                                 uint8_t* d_node_hashes, uint8_t* d_new_hashes, uint8_t* d_root, int device,
+                                 void* stream) {
+  g_err.clear();
+  int err;
+  if ((err = check_append_args(old_size, n, d_old_hashes, d_new_hashes, d_root, "d_"))) return err;
+  if (n && !d_leaf_hashes) return set_err(EDV_E_ARG, "merkle: null d_leaf_hashes");
+  for (const uint8_t* p : {d_old_hashes, d_leaf_hashes, static_cast<const uint8_t*>(d_node_hashes),
+                           static_cast<const uint8_t*>(d_new_hashes), static_cast<const uint8_t*>(d_root)})
+    if (reinterpret_cast<uintptr_t>(p) & 15) return set_err(EDV_E_ARG, "merkle: hash buffers must be 16-byte aligned");
+  CtxLock cl(device);
+  if (cl.err) return cl.err;
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : cl.c->stream;
+  if ((err = launch_merkle(*cl.c, old_size, d_old_hashes, nullptr, nullptr, 0, n, nullptr, d_node_hashes, d_new_hashes,
+                           d_root, s, nullptr, nullptr, n ? d_leaf_hashes : nullptr)))
+    return err;
+  if (!stream) HIPOK(hipStreamSynchronize(s), "stream sync");
+  return 0;
 }
 
 int edv_verify_batch_dev_flags(const uint8_t* d_sigs, const uint8_t* d_pks, const uint8_t* d_msgs,

@@ -117,6 +117,15 @@ def lib():
         for f in (h.edv_merkle_prove_inclusion_dev, h.edv_merkle_prove_consistency_dev):
             f.argtypes = [vp, vp, u64, vp, vp, vp, u64, u64, vp, vp, vp, vp, ctypes.c_int, vp]
             f.restype = ctypes.c_int
+        h.edv_merkle_audit_nodes.argtypes = [vp, vp, u64, u64, u64, vp, vp, ctypes.c_int]
+        h.edv_merkle_audit_nodes_dev.argtypes = [vp, vp, u64, u64, u64, vp, vp, ctypes.c_int, vp]
+        h.edv_merkle_audit_leaves.argtypes = [vp, u64, u64, vp, vp, u64, vp, vp, ctypes.c_int]
+        h.edv_merkle_audit_leaves_dev.argtypes = [vp, u64, u64, vp, vp, u64, u64, vp, vp, ctypes.c_int, vp]
+        h.edv_merkle_extend_hashed.argtypes = [u64, vp, vp, u64, vp, vp, vp, ctypes.c_int]
+        h.edv_merkle_extend_hashed_dev.argtypes = [u64, vp, vp, u64, vp, vp, vp, ctypes.c_int, vp]
+        for f in (h.edv_merkle_audit_nodes, h.edv_merkle_audit_nodes_dev, h.edv_merkle_audit_leaves,
+                  h.edv_merkle_audit_leaves_dev, h.edv_merkle_extend_hashed, h.edv_merkle_extend_hashed_dev):
+            f.restype = ctypes.c_int
         h.edv_verify_batch_dev_flags.argtypes = [vp, vp, vp, vp, u64, u64, vp, ctypes.c_int, vp, ctypes.c_uint32]
         h.edv_verify_batch_dev_flags.restype = ctypes.c_int
         h.edv_verify_batch_dev_pipelined.argtypes = [vp, vp, vp, vp, u64, u64, vp, ctypes.c_int, ctypes.c_uint32]
@@ -789,6 +798,119 @@ def merkle_prove_consistency_device(d_leaf_store, d_node_store, store_leaves, d_
     _check(lib().edv_merkle_prove_consistency_dev(d_leaf_store, d_node_store, store_leaves, d_first, d_second,
                                                   d_proof_off, proof_base, n, d_proofs, d_status, d_old_roots,
                                                   d_new_roots, device, stream))
+
+
+# auditing a stored tree (row f-9): one status byte per stored entry, EDV_AUDIT_* of include/edv.h
+AUDIT_UNCHECKED = 0    # never written by a kernel: what the host forms fill the buffer with first
+AUDIT_OK = 1
+AUDIT_BAD = 2
+AUDIT_NONE = (1 << 64) - 1   # a summary's lowest bad position when nothing is bad
+
+
+def _store_arrays(leaf_store, node_store, store_leaves):
+    store_leaves = int(store_leaves)
+    if not 0 <= store_leaves <= MERKLE_MAX_SIZE:
+        raise ValueError("store_leaves must be in [0, 2^62]")
+    leaf_store = _u8(leaf_store, "leaf_store", 32 * store_leaves)
+    if node_store is not None:
+        node_store = _u8(node_store, "node_store", 32 * (store_leaves - bin(store_leaves).count("1")))
+    return leaf_store, node_store, store_leaves
+
+
+def merkle_audit_nodes(leaf_store, node_store, store_leaves, node_lo=0, count=None, want_status=True, device: int = 0):
+    """Check nodes [node_lo, node_lo + count) of a hash store in host memory
+    (0-based positions; default: every node from node_lo on) against their
+    stored children (edv_merkle_audit_nodes, row f-9).  The call copies the
+    store prefix the slice reads to the device every time.
+
+    leaf_store / node_store as for merkle_prove_inclusion.  Returns (bad,
+    first_bad, status): the number of bad nodes, the lowest bad position (None
+    if there is none) and the AUDIT_* bytes of the slice (None unless wanted)."""
+    leaf_store, node_store, store_leaves = _store_arrays(leaf_store, node_store, store_leaves)
+    nodes = store_leaves - bin(store_leaves).count("1")
+    node_lo = int(node_lo)
+    count = nodes - node_lo if count is None else int(count)
+    if node_lo < 0 or count < 0 or node_lo + count > nodes:
+        raise ValueError("the slice reaches past the node store")
+    if count > MERKLE_MAX_LEAVES:
+        raise ValueError("more than MERKLE_MAX_LEAVES entries in one call")
+    status = np.zeros(count, dtype=np.uint8) if want_status else None
+    summary = np.zeros(2, dtype=np.uint64)
+    _check(lib().edv_merkle_audit_nodes(leaf_store.ctypes.data, node_store.ctypes.data, store_leaves, node_lo, count,
+                                        _ptr(status), summary.ctypes.data, device))
+    return int(summary[0]), (None if int(summary[1]) == AUDIT_NONE else int(summary[1])), status
+
+
+def merkle_audit_leaves(leaf_store, store_leaves, leaf_lo, leaves, offsets, want_status=True, device: int = 0):
+    """Check leaf-store entries leaf_lo .. leaf_lo + n - 1 (0-based) against the
+    n leaves laid out as msgs / offsets everywhere else (edv_merkle_audit_leaves).
+    Returns (bad, first_bad, status) as merkle_audit_nodes, positions in the
+    leaf store."""
+    leaf_store, _, store_leaves = _store_arrays(leaf_store, None, store_leaves)
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    if off.ndim != 1 or len(off) < 1:
+        raise ValueError("offsets must hold n + 1 entries")
+    n, leaf_lo = len(off) - 1, int(leaf_lo)
+    if leaf_lo < 0 or leaf_lo + n > store_leaves:
+        raise ValueError("the slice reaches past the leaf store")
+    if n > MERKLE_MAX_LEAVES:
+        raise ValueError("more than MERKLE_MAX_LEAVES entries in one call")
+    leaves = _u8(leaves, "leaves", int(off[-1]))
+    status = np.zeros(n, dtype=np.uint8) if want_status else None
+    summary = np.zeros(2, dtype=np.uint64)
+    _check(lib().edv_merkle_audit_leaves(leaf_store.ctypes.data, store_leaves, leaf_lo, leaves.ctypes.data,
+                                         off.ctypes.data, n, _ptr(status), summary.ctypes.data, device))
+    return int(summary[0]), (None if int(summary[1]) == AUDIT_NONE else int(summary[1])), status
+
+
+def merkle_audit_nodes_device(d_leaf_store, d_node_store, store_leaves, node_lo, count, d_status, d_summary, device=0,
+                              stream=None):
+    """Device-resident form (pointers are ints, None = NULL); async on `stream`
+    if given.  Adds into d_summary, two uint64 the caller set to (0, AUDIT_NONE)."""
+    _check(lib().edv_merkle_audit_nodes_dev(d_leaf_store, d_node_store, store_leaves, node_lo, count, d_status,
+                                            d_summary, device, stream))
+
+
+def merkle_audit_leaves_device(d_leaf_store, store_leaves, leaf_lo, d_leaves, d_leaf_off, n, d_status, d_summary,
+                               device=0, leaf_base=0, stream=None):
+    """Device-resident form, as merkle_audit_nodes_device."""
+    _check(lib().edv_merkle_audit_leaves_dev(d_leaf_store, store_leaves, leaf_lo, d_leaves, d_leaf_off, leaf_base, n,
+                                             d_status, d_summary, device, stream))
+
+
+def merkle_extend_hashed(old_size: int, old_hashes, leaf_hashes, want_node_hashes=True, device: int = 0):
+    """merkle_extend from the leaves' hashes instead of their bytes
+    (edv_merkle_extend_hashed, row f-9): leaf_hashes is n x 32 bytes (bytes or a
+    uint8 array).  Returns (node_hashes, new_hashes, root), byte-identical to
+    merkle_extend's on the leaves those hashes belong to."""
+    leaf_hashes = _u8(leaf_hashes, "leaf_hashes") if len(leaf_hashes) else np.zeros(0, dtype=np.uint8)
+    if leaf_hashes.nbytes % 32:
+        raise ValueError("leaf_hashes is not a whole number of hashes")
+    n, old_size = leaf_hashes.nbytes // 32, int(old_size)
+    if old_size < 0 or old_size + n > MERKLE_MAX_SIZE:
+        raise ValueError("tree size out of range")
+    if n > MERKLE_MAX_LEAVES:
+        raise ValueError("more than MERKLE_MAX_LEAVES leaves in one call")
+    if not isinstance(old_hashes, np.ndarray):
+        old_hashes = np.frombuffer(bytes(old_hashes), dtype=np.uint8)
+    if old_hashes.dtype != np.uint8 or not old_hashes.flags.c_contiguous:
+        raise ValueError("old_hashes must be contiguous uint8")
+    if old_hashes.nbytes != 32 * bin(old_size).count("1"):
+        raise ValueError("old_hashes size does not match old_size")
+    node_h = np.zeros((merkle_node_span(old_size, n), 32), dtype=np.uint8) if want_node_hashes else None
+    new_h = np.zeros((bin(old_size + n).count("1"), 32), dtype=np.uint8)
+    root = np.zeros(32, dtype=np.uint8)
+    _check(lib().edv_merkle_extend_hashed(old_size, old_hashes.ctypes.data if old_hashes.nbytes else None,
+                                          leaf_hashes.ctypes.data if n else None, n, _ptr(node_h), new_h.ctypes.data,
+                                          root.ctypes.data, device))
+    return node_h, new_h, root.tobytes()
+
+
+def merkle_extend_hashed_device(old_size, d_old_hashes, d_leaf_hashes, n, d_node_hashes, d_new_hashes, d_root, device=0,
+                                stream=None):
+    """Device-resident form (pointers are ints, None = NULL); async on `stream` if given."""
+    _check(lib().edv_merkle_extend_hashed_dev(old_size, d_old_hashes, d_leaf_hashes, n, d_node_hashes, d_new_hashes,
+                                              d_root, device, stream))
 
 
 def verify_detached_batch(items, device_mask: int = 0):

@@ -14,6 +14,8 @@ classes, written from their semantics:
   plenum/common/ledger_manager.py:564-609 hasValidCatchupReplies -> Ledger.verify_catchup_txns
   plenum/server/node.py:3024-3034         getReplyFromLedger: merkleInfo per reply -> merkleInfoBatch (row f-8)
   plenum/common/ledger_manager.py:995-998 a consistency proof and both roots -> consistency_proofs (row f-8)
+  ledger/ledger.py:70-114                 recoverTree trusts a store that has leaves -> auditHashStore,
+                                          recoverTreeVerified (row f-9)
 
 commitTxns(count) is one CompactMerkleTree.append_batch call
 (edv_merkle_append_batch from merkle.MIN_DEVICE_APPEND_LEAVES transactions
@@ -106,6 +108,42 @@ class Ledger:
         hashes = list(reversed(self.tree.inclusion_proof(treeSize, treeSize + 1)))
         self.tree._update(treeSize, hashes)
         self.tree.verify_consistency(len(self._transactionLog))
+
+    # ---- auditing the hash store (row f-9)
+    def auditHashStore(self, check_leaves=True):
+        """CompactMerkleTree.audit_store over the ledger's store, as a
+        merkle.StoreAudit: every stored node against its stored children, the
+        counts (against the log's length too), the tree's hashes; with
+        check_leaves every stored leaf hash against the log's transaction,
+        serialised again.  Nothing is changed."""
+        leaves = [self.serialize_for_tree(t) for t in self._transactionLog] if check_leaves else None
+        audit = self.tree.audit_store(leaves, on_device=self.on_device, device=self.device)
+        audit.counts_ok = audit.counts_ok and self.tree.leafCount == len(self._transactionLog)
+        return audit
+
+    def recoverTreeVerified(self):
+        """recoverTree that does not trust the store (ledger/ledger.py:70-114
+        trusts one that has leaves): "store" when the tree is recovered from
+        the hash store and the audit, leaves included, passes; "rebuilt" when
+        the stored leaf hashes are the log's and only nodes or counts are
+        wrong: the node store is recomputed from the leaf hashes
+        (CompactMerkleTree.rebuild_nodes), the log is not hashed again; else
+        "log": recoverTreeFromTxnLog."""
+        try:
+            self.recoverTreeFromHashStore()
+            recovered = True
+        except (ConsistencyVerificationFailed, IndexError):
+            recovered = False
+        audit = self.auditHashStore(check_leaves=True)
+        if recovered and audit.ok:
+            return "store"
+        n = len(self._transactionLog)
+        if self.tree.leafCount == n and audit.leaves_checked == n and not audit.bad_leaves:
+            self.tree.rebuild_nodes(on_device=self.on_device, device=self.device)
+            self.seqNo = self.tree.tree_size
+            return "rebuilt"
+        self.recoverTreeFromTxnLog()
+        return "log"
 
     # ---- committed transactions
     def add(self, txn):

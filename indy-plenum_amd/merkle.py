@@ -24,6 +24,16 @@ edv_merkle_prove_*_dev call for the batch (kernels
 edv_merkle_prove_inclusion_kernel / edv_merkle_prove_consistency_kernel),
 returning a ProofBatch in the layout the batched verification reads.
 
+Nothing in the reference checks the stored hashes those reads copy
+(ledger/ledger.py:70-114 recoverTree trusts a store that has leaves;
+compact_merkle_tree.py verify_consistency compares two counts).  `audit_store`
+(row f-9) checks every stored node against its stored children, and the leaf
+hashes against the leaves if given, one lane per entry over a DeviceHashStore
+(kernels edv_merkle_audit_nodes_kernel / edv_merkle_audit_leaves_kernel), and
+returns a StoreAudit; `rebuild_nodes` recomputes the node store from the leaf
+hashes and `extend_hashed` extends a tree from leaf hashes alone
+(edv_merkle_extend_hashed: the extend's passes, the first reading hashes).
+
 `append_batch` (row f-6) is `extend` that also returns what each `append`
 returns (ledger/ledger.py:145-155: the audit path, and the root hash read after
 it), one edv_merkle_append_batch call per batch (kernel
@@ -77,6 +87,17 @@ MIN_DEVICE_VERIFY_PROOFS = 64
 # "crossover": 113 us against 187 us for 16 merkleInfo proofs on 10,000
 # leaves, 114 us against 205 us on 2^20 + 12,345; nothing below 16 was measured)
 MIN_DEVICE_PROVE_PROOFS = 16
+
+
+# audit_store(on_device=None) over a DeviceHashStore takes the device from this
+# many entries (nodes, and leaves if given) on: the smallest measured node count
+# at which the route through the store's mirror beats the hashlib loop on both
+# stores, the node store alone and the node and leaf stores with 256-byte leaves
+# (profiles/r11/merkle_audit_bench.json, "crossover": at 256 nodes 49.3 us
+# against 239.2 us, and 149.1 us against 364.3 us with the 258 leaves; at 64
+# nodes the node store alone wins, 49.3 us against 61.1 us, and with the 66
+# leaves the loop does, 93.7 us against 134.5 us; at 16 the loop wins both)
+MIN_DEVICE_AUDIT_ENTRIES = 256
 
 
 class ConsistencyVerificationFailed(Exception):
@@ -241,6 +262,11 @@ class MemoryHashStore:
         self._nodes = bytearray()
         return True
 
+    def replaceNodes(self, hashes):
+        """The node store wholesale: k x 32 bytes, in position order (what
+        CompactMerkleTree.rebuild_nodes recomputed from the leaf hashes)."""
+        self._nodes = bytearray(self._bulk(hashes))
+
     def _check(self, h):
         if len(h) != self.HASH:
             raise ValueError("a hash is %d bytes" % self.HASH)
@@ -308,6 +334,16 @@ class DeviceHashStore(MemoryHashStore):
                 self._sent[k] = need
         return self._bufs[0].ptr, self._bufs[1].ptr, self.leafCount, self.nodeCount
 
+    def replaceNodes(self, hashes):
+        """MemoryHashStore's; the node mirror is uploaded again, whole, by the next device_arrays()."""
+        super().replaceNodes(hashes)
+        self._sent[1] = 0
+
+    def mark_stale(self):
+        """Both mirrors are uploaded again, whole, by the next device_arrays():
+        for a caller that changed the host bytes other than by appending."""
+        self._sent = [0, 0]
+
     def work_area(self, nbytes):
         """A device buffer of at least nbytes that the batch calls reuse."""
         if self._work is None or self._work.nbytes < nbytes:
@@ -354,6 +390,51 @@ class ProofBatch:
 
 def _hash_rows(hashes):
     return np.frombuffer(b"".join(hashes), dtype=np.uint8).reshape(-1, 32)
+
+
+class StoreAudit:
+    """What CompactMerkleTree.audit_store found (row f-9).  `nodes_checked`
+    and `leaves_checked` count the entries compared; `bad_nodes` and
+    `bad_leaves` are the sorted 1-based positions, as readNode and readLeaf
+    count, of the nodes that are not the hash of their stored children and of
+    the leaf hashes that are not the hash of their leaf; `counts_ok`: the node
+    store has exactly the nodes its leaf count implies (and, with leaves given,
+    there is one leaf per stored hash); `frontier_ok`: the tree's own size and
+    hashes are what the store holds for them."""
+
+    def __init__(self, nodes_checked=0, bad_nodes=(), leaves_checked=0, bad_leaves=(), counts_ok=True,
+                 frontier_ok=True):
+        self.nodes_checked = nodes_checked
+        self.bad_nodes = sorted(bad_nodes)
+        self.leaves_checked = leaves_checked
+        self.bad_leaves = sorted(bad_leaves)
+        self.counts_ok = counts_ok
+        self.frontier_ok = frontier_ok
+
+    @property
+    def ok(self):
+        return self.counts_ok and self.frontier_ok and not self.bad_nodes and not self.bad_leaves
+
+    def __repr__(self):
+        return "StoreAudit(nodes_checked=%d, bad_nodes=%r, leaves_checked=%d, bad_leaves=%r, counts_ok=%r, " \
+            "frontier_ok=%r)" % (self.nodes_checked, self.bad_nodes, self.leaves_checked, self.bad_leaves,
+                                 self.counts_ok, self.frontier_ok)
+
+
+def _carry_chain(hasher, size, stack, leaf_hashes):
+    """The appends' carry chain over leaf hashes: (size, stack, node hashes in store order)."""
+    nodes = []
+    for h in leaf_hashes:
+        size += 1
+        stack.append(h)
+        s = size
+        while not s & 1:
+            right = stack.pop()
+            left = stack.pop()
+            stack.append(hasher.hash_children(left, right))
+            nodes.append(stack[-1])
+            s >>= 1
+    return size, stack, nodes
 
 
 class CompactMerkleTree:
@@ -724,6 +805,199 @@ class CompactMerkleTree:
             if s <= 0:
                 raise ValueError("seqNo must be > 0, got %r" % (s,))
         return self.inclusion_proof_batch([(s - 1, s) for s in seq_nos], on_device, device, want_roots)
+
+    # ---- auditing and repairing the store (row f-9)
+    def _extend_hashed_parts(self, size, hashes, blob, on_device, step, device):
+        """(size, hashes) extended by the leaf hashes in blob (n x 32 bytes) ->
+        (size, hashes, [node bytes per call])."""
+        hashes, parts = list(hashes), []
+        for lo in range(0, len(blob), 32 * step):
+            part = blob[lo:lo + 32 * step]
+            if on_device:
+                node_h, new_h, _ = edv.merkle_extend_hashed(size, b"".join(hashes), part, device=device)
+                size, hashes = size + len(part) // 32, [bytes(r) for r in new_h]
+                parts.append(node_h.tobytes())
+            else:
+                size, hashes, nodes = _carry_chain(self.__hasher, size, hashes,
+                                                   [part[k:k + 32] for k in range(0, len(part), 32)])
+                parts.append(b"".join(nodes))
+        return size, hashes, parts
+
+    def _hashed_route(self, n, on_device, max_call):
+        if on_device is None:
+            on_device = n >= MIN_DEVICE_LEAVES
+        if on_device and self.__hasher.hashfunc is not hashlib.sha256:
+            raise ValueError("the device extends SHA-256 trees only")
+        step = edv.MERKLE_MAX_LEAVES if max_call is None else int(max_call)
+        if step < 1 or step > edv.MERKLE_MAX_LEAVES:
+            raise ValueError("max_call must be in [1, %d]" % edv.MERKLE_MAX_LEAVES)
+        return on_device, step
+
+    def extend_hashed(self, leaf_hashes, on_device=None, max_call=None, device=0):
+        """extend from the leaves' hashes instead of their bytes (a store
+        loaded from disk, a catch-up peer that sends hashes): leaf_hashes is a
+        list of 32-byte hashes, their concatenation, or an (n, 32) uint8 array.
+        Tree and hash store end byte-identical to extend on the leaves those
+        hashes belong to.  on_device as extend (edv_merkle_extend_hashed per
+        max_call hashes; None: from MIN_DEVICE_LEAVES hashes on, the extend's
+        own threshold)."""
+        if isinstance(leaf_hashes, np.ndarray):
+            blob = np.ascontiguousarray(leaf_hashes, dtype=np.uint8).tobytes()
+        elif isinstance(leaf_hashes, (bytes, bytearray, memoryview)):
+            blob = bytes(leaf_hashes)
+        else:
+            blob = b"".join(_hash32(h, "a leaf hash") for h in leaf_hashes)
+        if len(blob) % 32:
+            raise ValueError("not a whole number of hashes")
+        on_device, step = self._hashed_route(len(blob) // 32, on_device, max_call)
+        if self.__tree_size + len(blob) // 32 > edv.MERKLE_MAX_SIZE:
+            raise ValueError("tree size above 2^62")
+        size, hashes, parts = self._extend_hashed_parts(self.__tree_size, self.__hashes, blob, on_device, step, device)
+        self.__hashStore.writeLeafs(blob)
+        self.__hashStore.writeNodes(b"".join(parts))
+        self._update(size, hashes)
+
+    def rebuild_nodes(self, on_device=None, device=0):
+        """Recompute the node store from the leaf store, without the leaves:
+        extend_hashed from an empty tree over the stored leaf hashes, in
+        edv.MERKLE_MAX_LEAVES slices; the result replaces the node store
+        (hashStore.replaceNodes) and the tree's size and hashes."""
+        leafs, _ = self._store_bytes()
+        blob = bytes(leafs)
+        on_device, step = self._hashed_route(len(blob) // 32, on_device, None)
+        size, hashes, parts = self._extend_hashed_parts(0, (), blob, on_device, step, device)
+        self.__hashStore.replaceNodes(b"".join(parts))
+        self._update(size, hashes)
+
+    def _audit_route(self, entries, on_device):
+        """"host", "store" or "copy", as _prove_route."""
+        mirrored = isinstance(self.__hashStore, DeviceHashStore)
+        if on_device is None:
+            on_device = mirrored and entries >= MIN_DEVICE_AUDIT_ENTRIES
+        if not on_device:
+            return "host"
+        if self.__hasher.hashfunc is not hashlib.sha256:
+            raise ValueError("the device audits SHA-256 trees only")
+        return "store" if mirrored else "copy"
+
+    def _stored_frontier(self, size):
+        """The hashes of the tree of `size` leaves as the store holds them, largest first (None: not all there)."""
+        store, out = self.__hashStore, []
+        try:
+            for b in reversed(range(size.bit_length())):
+                if (size >> b) & 1:
+                    k = (size >> b) - 1
+                    out.append(store.readLeaf(k + 1) if b == 0 else store.readNode(node_position(b, k)))
+        except IndexError:
+            return None
+        return out
+
+    def _audit_nodes_host(self, leafs, nodes, count):
+        """Nodes 0 .. count - 1 in hashlib, in store order: leaf s (1-based) wrote heights 1 .. ctz(s)."""
+        bad, q, s, hasher = [], 0, 2, self.__hasher
+        while q < count:
+            h, t = 1, s
+            while not t & 1 and q < count:
+                k = (s >> h) - 1
+                if h == 1:
+                    left, right = leafs[64 * k:64 * k + 32], leafs[64 * k + 32:64 * k + 64]
+                else:
+                    pl, pr = node_position(h - 1, 2 * k) - 1, node_position(h - 1, 2 * k + 1) - 1
+                    left, right = nodes[32 * pl:32 * pl + 32], nodes[32 * pr:32 * pr + 32]
+                if hasher.hash_children(bytes(left), bytes(right)) != nodes[32 * q:32 * q + 32]:
+                    bad.append(q + 1)
+                q += 1
+                h += 1
+                t >>= 1
+            s += 2
+        return bad
+
+    def _audit_store_device(self, ncheck, leaves, device):
+        """-> (bad node positions, bad leaf positions), 1-based, through the mirror of a DeviceHashStore."""
+        store = self.__hashStore
+        d_leafs, d_nodes, nleaves, _ = store.device_arrays()
+        empty = np.array([0, edv.AUDIT_NONE], dtype=np.uint64)
+        bad_nodes, bad_leaves = [], []
+        if ncheck:
+            # summary | one status byte per node: every slice adds into the one summary, which alone comes back
+            work = store.work_area(16 + ncheck)
+            work.upload(empty)
+            for lo in range(0, ncheck, edv.MERKLE_MAX_LEAVES):
+                cnt = min(edv.MERKLE_MAX_LEAVES, ncheck - lo)
+                edv.merkle_audit_nodes_device(d_leafs, d_nodes, nleaves, lo, cnt, work.ptr + 16 + lo, work.ptr,
+                                              device=device)
+            if int(work.download(16, np.uint64)[0]):
+                bad_nodes = (np.flatnonzero(work.download_at(16, ncheck) != edv.AUDIT_OK) + 1).tolist()
+        for lo in range(0, len(leaves), edv.MERKLE_MAX_LEAVES):
+            part = leaves[lo:lo + edv.MERKLE_MAX_LEAVES]
+            n = len(part)
+            off = np.zeros(n + 1, dtype=np.uint64)
+            off[1:] = np.cumsum([len(x) for x in part], dtype=np.uint64)
+            part.append(b"\0" * 8)
+            blob = np.frombuffer(b"".join(part), dtype=np.uint8)
+            # summary | offsets | leaf bytes (8 readable past the end) | statuses
+            o_off, o_blob = 16, 16 + 8 * (n + 1)
+            o_st = o_blob + len(blob)
+            work = store.work_area(o_st + n)
+            p = work.ptr
+            work.upload(np.concatenate([empty, off]))
+            edv._check(edv.lib().edv_h2d(store.device, p + o_blob, blob.ctypes.data, blob.nbytes))
+            edv.merkle_audit_leaves_device(d_leafs, nleaves, lo, p + o_blob, p + o_off, n, p + o_st, p, device=device)
+            if int(work.download(16, np.uint64)[0]):
+                bad_leaves += (np.flatnonzero(work.download_at(o_st, n) != edv.AUDIT_OK) + 1 + lo).tolist()
+        return bad_nodes, bad_leaves
+
+    def audit_store(self, leaves=None, on_device=None, device=0):
+        """Check the hash store, which recovery otherwise trusts: the node
+        count against get_expected_node_count; every node against its two
+        stored children; with `leaves` (the leaves' bytes, in order) every
+        stored leaf hash against its leaf; the tree's own size and hashes
+        against what the store holds for them.  Returns a StoreAudit.
+
+        Routed as the batched proofs: over a DeviceHashStore the device forms
+        on its mirror (edv_merkle_audit_nodes_dev / _leaves_dev; 16 bytes come
+        back unless something is bad), from MIN_DEVICE_AUDIT_ENTRIES entries on
+        with on_device None; on_device True over another store is the
+        host-buffer forms, which copy the store per call; otherwise the same
+        checks in hashlib."""
+        store = self.__hashStore
+        nleaves, nnodes = store.leafCount, store.nodeCount
+        expected = self.get_expected_node_count(nleaves)
+        # a node past the expected count has no children to check; one that is missing is a count error
+        ncheck = min(nnodes, expected)
+        counts_ok = nnodes == expected
+        if leaves is not None:
+            leaves = [bytes(x) for x in leaves]
+            counts_ok = counts_ok and len(leaves) == nleaves
+            leaves = leaves[:nleaves]
+        lcheck = len(leaves) if leaves is not None else 0
+        frontier_ok = self.__tree_size == nleaves and self._stored_frontier(nleaves) == list(self.__hashes)
+        route = self._audit_route(ncheck + lcheck, on_device)
+        if route == "store":
+            bad_nodes, bad_leaves = self._audit_store_device(ncheck, leaves or [], device)
+        elif route == "copy":
+            leafs, nodes = self._store_bytes()
+            leafs, nodes = bytes(leafs), bytes(nodes)[:32 * expected].ljust(32 * expected, b"\0")
+            bad_nodes, bad_leaves = [], []
+            for lo in range(0, ncheck, edv.MERKLE_MAX_LEAVES):
+                cnt = min(edv.MERKLE_MAX_LEAVES, ncheck - lo)
+                bad, _, status = edv.merkle_audit_nodes(leafs, nodes, nleaves, lo, cnt, device=device)
+                if bad:
+                    bad_nodes += (np.flatnonzero(status != edv.AUDIT_OK) + 1 + lo).tolist()
+            for lo in range(0, lcheck, edv.MERKLE_MAX_LEAVES):
+                part = leaves[lo:lo + edv.MERKLE_MAX_LEAVES]
+                off = np.zeros(len(part) + 1, dtype=np.uint64)
+                off[1:] = np.cumsum([len(x) for x in part], dtype=np.uint64)
+                bad, _, status = edv.merkle_audit_leaves(leafs, nleaves, lo, b"".join(part) + b"\0" * 8, off,
+                                                         device=device)
+                if bad:
+                    bad_leaves += (np.flatnonzero(status != edv.AUDIT_OK) + 1 + lo).tolist()
+        else:
+            leafs, nodes = self._store_bytes()
+            bad_nodes = self._audit_nodes_host(leafs, nodes, ncheck)
+            bad_leaves = [i + 1 for i in range(lcheck)
+                          if self.__hasher.hash_leaf(leaves[i]) != leafs[32 * i:32 * i + 32]]
+        return StoreAudit(ncheck, bad_nodes, lcheck, bad_leaves, counts_ok, frontier_ok)
 
     def get_tree_head(self, seq=None):
         if seq is None:

@@ -58,6 +58,19 @@ base58 encoding of the 10,000 merkleInfo replies on a line of its own, and
 from which (b) wins on both trees is MIN_DEVICE_PROVE_PROOFS.  The routes of a
 case are timed interleaved: every repetition visits each route in turn.
 
+With --leg audit: the hash-store audit and repair (row f-9), written to
+profiles/r11/merkle_audit_bench.json.  Two ledgers of 256-byte transactions
+over a DeviceHashStore, 10,000 leaves and 2^20 + 12,345:
+  a  edv_merkle_audit_nodes_dev / _leaves_dev / edv_merkle_extend_hashed_dev   device-resident (copies of the
+     store of the bench's own), HIP events; the extend from hashes hashes as many nodes as the node audit checks,
+     with coalesced loads; the leaf audit streams its input: both are the node audit's gathers' yardsticks
+  b  CompactMerkleTree.audit_store(on_device=True), with and without the leaves, and rebuild_nodes(on_device=True),
+     through the DeviceHashStore
+  e  the same three in hashlib (on_device=False)
+  r  Ledger.recoverTreeFromTxnLog on the device, the remedy there was before, and recoverTreeVerified on a clean store
+and (b) against (e) on stores of 16, 64, 256 and 1,024 nodes, alone and with their leaves, whose smallest size from
+which (b) wins both ways is MIN_DEVICE_AUDIT_ENTRIES.
+
 Every figure is wall clock around calls that end in a device synchronise (the
 device forms with stream = NULL synchronise the library stream before they
 return), the median of 5 repetitions after a warm-up; a repetition repeats
@@ -299,6 +312,126 @@ def prove_leg(args, rng):
     return res
 
 
+AUDIT_SMALL = (16, 64, 256, 1024)
+
+
+def audit_leg(args, rng):
+    """The hash-store audit and repair against the hashlib loop and against
+    recovery from the log (module docstring)."""
+    from indy_plenum_amd.ledger import Ledger
+    hip = Hip()
+    res = {"window_s": args.window, "version": edv.version(), "leaf_bytes": LEAF_BYTES, "rows": [], "crossover": []}
+    empty = np.array([0, edv.AUDIT_NONE], dtype=np.uint64)
+
+    def build(size):
+        blob = rng.integers(0, 256, size * LEAF_BYTES + 8, dtype=np.uint8)
+        raw = blob.tobytes()
+        leaves = [raw[i * LEAF_BYTES:(i + 1) * LEAF_BYTES] for i in range(size)]
+        led = Ledger(tree=merkle.CompactMerkleTree(hashStore=merkle.DeviceHashStore(args.device)), on_device=True,
+                     device=args.device)
+        led._transactionLog = leaves
+        led.recoverTreeFromTxnLog()
+        return blob, leaves, led
+
+    for size in PROVE_TREES:
+        blob, leaves, led = build(size)
+        tree, store = led.tree, led.tree.hashStore
+        nleaves, nnodes = store.leafCount, store.nodeCount
+        good_nodes = bytes(store._nodes)
+        # the device-resident routes read copies of their own: recovery from the log resets the store and its mirror
+        own = (dev(np.frombuffer(bytes(store._leafs), np.uint8)), dev(np.frombuffer(good_nodes, np.uint8)))
+        d_leafs, d_nodes = own[0].ptr, own[1].ptr
+        d_blob = dev(blob)
+        d_off = dev(np.arange(size + 1, dtype=np.uint64) * np.uint64(LEAF_BYTES))
+        d_status, d_summary = edv.DeviceBuffer(max(size, 1)), dev(empty)
+        d_out = edv.DeviceBuffer(32 * (nnodes + 130))
+        slices = [(lo, min(edv.MERKLE_MAX_LEAVES, nnodes - lo)) for lo in range(0, nnodes, edv.MERKLE_MAX_LEAVES)]
+
+        def audit_nodes(stream):
+            for lo, cnt in slices:
+                edv.merkle_audit_nodes_device(d_leafs, d_nodes, nleaves, lo, cnt, d_status.ptr, d_summary.ptr,
+                                              device=args.device, stream=stream)
+
+        def audit_leaves(stream):
+            edv.merkle_audit_leaves_device(d_leafs, nleaves, 0, d_blob.ptr, d_off.ptr, size, d_status.ptr, d_summary.ptr,
+                                           device=args.device, stream=stream)
+
+        def extend_hashed(stream):   # the rebuild, device-resident: as many node hashes as the node audit, loads coalesced
+            edv.merkle_extend_hashed_device(0, None, d_leafs, size, d_out.ptr, d_out.ptr + 32 * nnodes,
+                                            d_out.ptr + 32 * (nnodes + 64), device=args.device, stream=stream)
+
+        # results first: a clean store is clean by every route, a damaged node is found alike, the rebuild restores it
+        audit_nodes(None)
+        audit_leaves(None)
+        extend_hashed(None)
+        assert d_summary.download(16, np.uint64).tolist() == empty.tolist()
+        assert d_out.download(32 * nnodes).tobytes() == good_nodes
+        want = tree.audit_store(leaves if size == PROVE_TREES[0] else None, on_device=False)
+        assert want.ok and tree.audit_store(leaves, on_device=True, device=args.device).ok
+        q = nnodes // 2
+        store._nodes[32 * q + 3] ^= 4
+        store.mark_stale()
+        got = tree.audit_store(on_device=True, device=args.device)
+        assert got.bad_nodes and q + 1 in got.bad_nodes and len(got.bad_nodes) <= 2
+        if size == PROVE_TREES[0]:
+            assert got.bad_nodes == tree.audit_store(on_device=False).bad_nodes
+        tree.rebuild_nodes(on_device=True, device=args.device)
+        assert bytes(store._nodes) == good_nodes and led.recoverTreeVerified() == "store"
+
+        routes = {"a_audit_nodes_dev": audit_nodes, "a_audit_leaves_dev": audit_leaves,
+                  "a_extend_hashed_dev": extend_hashed,
+                  "b_audit_store_nodes": lambda: tree.audit_store(on_device=True, device=args.device),
+                  "b_audit_store_nodes_and_leaves": lambda: tree.audit_store(leaves, on_device=True, device=args.device),
+                  "b_rebuild_nodes": lambda: tree.rebuild_nodes(on_device=True, device=args.device),
+                  "e_hashlib_nodes": lambda: tree.audit_store(on_device=False),
+                  "e_hashlib_nodes_and_leaves": lambda: tree.audit_store(leaves, on_device=False),
+                  "e_hashlib_rebuild_nodes": lambda: tree.rebuild_nodes(on_device=False),
+                  "r_recover_from_txn_log_device": led.recoverTreeFromTxnLog,
+                  "r_recover_tree_verified": led.recoverTreeVerified}
+        t = timed_interleaved(routes, args.window, reps=5 if size == PROVE_TREES[0] else 3, hip=hip)
+        row = {"tree": size, "nodes": nnodes, "leaves": size}
+        row.update(t)
+        us = lambda k: t[k]["median_us"]  # noqa: E731
+        row["ns_per_node_audit_dev"] = 1e3 * us("a_audit_nodes_dev") / nnodes
+        row["ns_per_node_extend_hashed_dev"] = 1e3 * us("a_extend_hashed_dev") / nnodes
+        row["audit_over_extend_hashed_dev"] = us("a_audit_nodes_dev") / us("a_extend_hashed_dev")
+        # the gathering node audit against the streaming leaf audit, per SHA-256 compression: a node is two blocks,
+        # a leaf of LEAF_BYTES with its prefix and padding (LEAF_BYTES + 1 + 9 + 63) // 64
+        leaf_blocks = (LEAF_BYTES + 1 + 9 + 63) // 64
+        row["ns_per_compression_audit_nodes_dev"] = 1e3 * us("a_audit_nodes_dev") / (2 * nnodes)
+        row["ns_per_compression_audit_leaves_dev"] = 1e3 * us("a_audit_leaves_dev") / (leaf_blocks * size)
+        row["hashlib_nodes_over_b"] = us("e_hashlib_nodes") / us("b_audit_store_nodes")
+        row["hashlib_nodes_and_leaves_over_b"] = us("e_hashlib_nodes_and_leaves") / us("b_audit_store_nodes_and_leaves")
+        row["recover_from_log_over_b_rebuild"] = us("r_recover_from_txn_log_device") / us("b_rebuild_nodes")
+        row["recover_from_log_over_b_audit_nodes"] = us("r_recover_from_txn_log_device") / us("b_audit_store_nodes")
+        res["rows"].append(row)
+        print(json.dumps(row), flush=True)
+        store.reset()
+    # (b) against (e) on small stores: trees of n + 2 leaves have n nodes
+    for n in AUDIT_SMALL:
+        blob, leaves, led = build(n + 2)
+        tree = led.tree
+        assert tree.nodeCount == n
+        for case, lv in (("nodes", None), ("nodes_and_leaves", leaves)):
+            t = timed_interleaved({"b_device_hash_store": lambda: tree.audit_store(lv, on_device=True, device=args.device),
+                                   "e_hashlib": lambda: tree.audit_store(lv, on_device=False)}, args.window)
+            row = dict(t, nodes=n, case=case, entries=n + (n + 2 if lv else 0))
+            row["b_beats_e"] = t["b_device_hash_store"]["median_us"] < t["e_hashlib"]["median_us"]
+            res["crossover"].append(row)
+            print(json.dumps(row), flush=True)
+        tree.hashStore.reset()
+    cross = None
+    for n in sorted(AUDIT_SMALL, reverse=True):
+        if all(r["b_beats_e"] for r in res["crossover"] if r["nodes"] == n):
+            cross = n
+        else:
+            break
+    res["min_device_audit_entries"] = {"value": cross, "rule": "smallest measured node count from which b < e on both "
+                                       "stores (the node store alone, and the node and leaf stores with 256-byte "
+                                       "leaves), at that count and every larger one measured; null: at none"}
+    return res
+
+
 def lane_efficiency(old, n, lanes=64):
     """The fold's trip counts (popcount(s) - 1 node hashes for s = old + i + 1) over the append kernel's
     waves of `lanes` consecutive leaves: (mean over waves of mean / max trips, fold hashes per leaf)."""
@@ -483,7 +616,7 @@ def verify_leg(args, rng):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=("extend", "append", "verify", "prove"), default="extend")
+    ap.add_argument("--leg", choices=("extend", "append", "verify", "prove", "audit"), default="extend")
     ap.add_argument("--out", default=None)
     ap.add_argument("--window", type=float, default=0.2)
     ap.add_argument("--device", type=int, default=0)
@@ -492,12 +625,13 @@ def main():
         args.out = {"extend": os.path.join(ROOT, "profiles", "r07", "merkle_bench.json"),
                     "append": os.path.join(ROOT, "profiles", "r08", "merkle_append_bench.json"),
                     "verify": os.path.join(ROOT, "profiles", "r09", "merkle_verify_bench.json"),
-                    "prove": os.path.join(ROOT, "profiles", "r10", "merkle_prove_bench.json")}[args.leg]
+                    "prove": os.path.join(ROOT, "profiles", "r10", "merkle_prove_bench.json"),
+                    "audit": os.path.join(ROOT, "profiles", "r11", "merkle_audit_bench.json")}[args.leg]
     if edv.device_count() < 1:
         sys.exit("bench_merkle needs a gfx950 GPU")
     rng = np.random.default_rng(0x6962)
-    if args.leg in ("append", "verify", "prove"):
-        res = {"append": append_leg, "verify": verify_leg, "prove": prove_leg}[args.leg](args, rng)
+    if args.leg in ("append", "verify", "prove", "audit"):
+        res = {"append": append_leg, "verify": verify_leg, "prove": prove_leg, "audit": audit_leg}[args.leg](args, rng)
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump(res, f, indent=1)
