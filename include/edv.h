@@ -494,6 +494,56 @@ int edv_merkle_extend_hashed_dev(uint64_t old_size, const uint8_t *d_old_hashes,
                                  int device, void *stream);
 
 /*
+ * Catch-up (row f-10): verify and apply the replies of a catch-up in one call.
+ * A joining node (plenum/common/ledger_manager.py:505-609 hasValidCatchupReplies
+ * / _add_txn) builds a temporary tree over each reply's transactions, walks one
+ * consistency proof from it to the catch-up target and then appends the
+ * transactions one by one: every transaction is hashed twice, one reply at a
+ * time.  Here the n leaves are the transactions of `replies` in-order replies,
+ * laid out as for edv_merkle_extend; the extend's passes hash them once, and
+ * one lane per reply folds the root of the tree at the reply's end and walks
+ * the reply's proof to (final_size, final_root).
+ *
+ *   reply_end   replies words: leaves of the call in replies 0 .. k (never
+ *               falling; an empty reply repeats the end before it; the last is n)
+ *   final_size / final_root   the catch-up target (the reference's catchUpTill)
+ *   proofs / proof_off   packed 32-byte entries and replies + 1 offsets in
+ *               entries, as for edv_merkle_verify_consistency
+ *   leaf_hashes / node_hashes   as edv_merkle_extend's, NULL: not wanted (the
+ *               lanes read them either way: the device form keeps them in
+ *               context scratch then)
+ *   reply_roots NULL, or replies x 32 bytes: the tree head at each reply's end
+ *               (zeros where the status is EDV_PROOF_RANGE)
+ *   status      replies bytes: EDV_PROOF_RANGE where reply_end[k] > n or
+ *               old_size + reply_end[k] > final_size, else what
+ *               edv_merkle_verify_consistency gives for (old_size + reply_end[k],
+ *               final_size, that head, final_root, proof k)
+ *
+ * The replies a caller may apply are the leading ones with EDV_PROOF_OK: a
+ * status after the first failure is computed over rejected transactions.
+ * EDV_E_ARG (host form) before anything is launched or written: every case of
+ * edv_merkle_extend; replies = 0 with n > 0; replies > n + 1; reply_end
+ * falling or not ending at n; proof_off falling; final_root, status, reply_end
+ * or proof_off NULL.  The device form's arrays live on the device and are not
+ * checked: an end past n is EDV_PROOF_RANGE, other inconsistencies are the
+ * caller's.  Alignment: hash buffers (d_final_root and d_proofs included) on
+ * 16 bytes, d_leaf_off, d_reply_end and d_proof_off on 8.  The device form
+ * shares the extend's scratch and its ordering across streams; the host form
+ * fills status with EDV_PROOF_UNVERIFIED, stages where the extend and verify
+ * host forms stage (edv_context_memory out[2], edv_trim, edv_release) and is
+ * synchronous.
+ */
+int edv_merkle_catchup(uint64_t old_size, const uint8_t *old_hashes, const uint8_t *leaves, const uint64_t *leaf_off,
+                       uint64_t n, const uint64_t *reply_end, uint64_t replies, uint64_t final_size,
+                       const uint8_t *final_root, const uint8_t *proofs, const uint64_t *proof_off,
+                       uint8_t *leaf_hashes, uint8_t *node_hashes, uint8_t *reply_roots, uint8_t *status, int device);
+int edv_merkle_catchup_dev(uint64_t old_size, const uint8_t *d_old_hashes, const uint8_t *d_leaves,
+                           const uint64_t *d_leaf_off, uint64_t leaf_base, uint64_t n, const uint64_t *d_reply_end,
+                           uint64_t replies, uint64_t final_size, const uint8_t *d_final_root, const uint8_t *d_proofs,
+                           const uint64_t *d_proof_off, uint64_t proof_base, uint8_t *d_leaf_hashes,
+                           uint8_t *d_node_hashes, uint8_t *d_reply_roots, uint8_t *d_status, int device, void *stream);
+
+/*
  * Pipelined submission of device-resident batches (a continuous stream of
  * client batches, e.g. one per Node prod): enqueues the batch and returns
  * without waiting.  Consecutive submissions alternate between two internal

@@ -11,14 +11,15 @@ client-inbox batch to the HIP kernels through the C-ABI in include/edv.h.
 """
 __version__ = "0.1.0"
 
-__all__ = ["Ledger", "MerkleVerifier", "STH", "verify_merkle_proofs", "DeviceHashStore", "ProofBatch", "StoreAudit"]
+__all__ = ["Ledger", "MerkleVerifier", "STH", "verify_merkle_proofs", "DeviceHashStore", "ProofBatch", "StoreAudit",
+           "CatchupResult"]
 
 
-def __getattr__(name):  # the ledger (rows f-6 to f-9), imported on first use
+def __getattr__(name):  # the ledger (rows f-6 to f-10), imported on first use
     if name in ("Ledger", "verify_merkle_proofs"):
         from . import ledger
         return getattr(ledger, name)
-    if name in ("MerkleVerifier", "STH", "DeviceHashStore", "ProofBatch", "StoreAudit"):
+    if name in ("MerkleVerifier", "STH", "DeviceHashStore", "ProofBatch", "StoreAudit", "CatchupResult"):
         from . import merkle
         return getattr(merkle, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

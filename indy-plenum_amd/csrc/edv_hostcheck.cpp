@@ -955,4 +955,54 @@ void hc_merkle_extend_hashed_needs(uint64_t old_size, uint64_t n, int host_form,
 }
 // out: kAuditUnchecked, kAuditOk, kAuditBad
 void hc_merkle_audit_consts(int32_t* out) { out[0] = kAuditUnchecked; out[1] = kAuditOk; out[2] = kAuditBad; }
+
+// ---- catch-up (edv_merkle.h, row f-10)
+// edv_merkle_catchup's signature minus `device`, and its EDV_E_ARG cases (-1):
+// hc_merkle_extend, then the catch-up kernel's lanes one after another over the
+// hashes it wrote.  Ends, offsets, hashes, proofs and outputs are heap blocks of
+// exactly their documented sizes: a lane reading an entry past its proof or a
+// hash past the call's is ASan's to see.
+int hc_merkle_catchup(uint64_t old_size, const uint8_t* old_hashes, const uint8_t* leaves, const uint64_t* off,
+                      uint64_t n, const uint64_t* reply_end, uint64_t replies, uint64_t final_size,
+                      const uint8_t* final_root, const uint8_t* proofs, const uint64_t* proof_off, uint8_t* leaf_hashes,
+                      uint8_t* node_hashes, uint8_t* reply_roots, uint8_t* status) {
+  if (n > (uint64_t(1) << 22) || old_size > kMerkleMaxSize || old_size + n > kMerkleMaxSize) return -1;
+  if ((old_size && !old_hashes) || !reply_end || !final_root || !proof_off || !status) return -1;
+  if ((replies == 0 && n) || replies > n + 1) return -1;
+  if (n && (!off || !hc_offsets_ok(off, n) || (!leaves && off[n] != off[0]))) return -1;
+  if (replies == 0) return 0;
+  if (!hc_offsets_ok(reply_end, replies - 1) || reply_end[replies - 1] != n || !hc_offsets_ok(proof_off, replies)) return -1;
+  if (!proofs && proof_off[replies] != proof_off[0]) return -1;
+  memset(status, kProofUnverified, replies);
+  const uint64_t nodes = merkle_node_count(old_size + n) - merkle_node_count(old_size);
+  const size_t nold = size_t(popc64(old_size));
+  std::vector<uint8_t> lh(32 * n + 1), nh(32 * nodes + 1), newh(32 * size_t(popc64(old_size + n)) + 1), root(32);
+  if (const int rc = hc_merkle_extend(old_size, old_hashes, leaves, off, n, lh.data(), nh.data(), newh.data(), root.data()))
+    return rc;
+  const uint64_t pbase = proof_off[0], entries = proof_off[replies] - proof_off[0];
+  std::vector<uint32_t> oldw(8 * nold), leafw(8 * n), nodew(8 * nodes), targetw(8), proofw(8 * entries);
+  std::vector<uint32_t> rootsw(reply_roots ? 8 * replies : 0);
+  std::vector<uint64_t> ends(reply_end, reply_end + replies), poff(proof_off, proof_off + replies + 1);
+  std::vector<uint8_t> st(replies);
+  if (nold) memcpy(oldw.data(), old_hashes, 32 * nold);
+  if (n) memcpy(leafw.data(), lh.data(), 32 * n);
+  if (nodes) memcpy(nodew.data(), nh.data(), 32 * nodes);
+  memcpy(targetw.data(), final_root, 32);
+  if (entries) memcpy(proofw.data(), proofs + 32 * pbase, 32 * entries);
+  const MerkleCatchup a = merkle_catchup_args(old_size, n, oldw.data(), leafw.data(), nodew.data(), ends.data(), replies,
+                                              final_size, targetw.data(), proofw.data(), poff.data(), pbase,
+                                              reply_roots ? rootsw.data() : nullptr, st.data());
+  for (uint64_t k = 0; k < replies; k++) merkle_catchup_lane(a, k);
+  memcpy(status, st.data(), replies);
+  if (reply_roots) memcpy(reply_roots, rootsw.data(), 32 * replies);
+  if (leaf_hashes && n) memcpy(leaf_hashes, lh.data(), 32 * n);
+  if (node_hashes && nodes) memcpy(node_hashes, nh.data(), 32 * nodes);
+  return 0;
+}
+// the host plan of both forms, a whole row of kMerkleBufs = 20
+void hc_merkle_catchup_needs(uint64_t old_size, uint64_t n, uint64_t mbytes, uint64_t replies, uint64_t entries,
+                             int host_form, int want_leaf, int want_node, int want_roots, uint64_t* out20) {
+  const MerkleSizes s = merkle_catchup_needs(old_size, n, mbytes, replies, entries, host_form, want_leaf, want_node, want_roots);
+  memcpy(out20, s.data(), sizeof s);
+}
 }

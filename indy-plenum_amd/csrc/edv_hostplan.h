@@ -265,4 +265,38 @@ inline MerkleSizes merkle_extend_hashed_needs(uint64_t old_size, uint64_t n, boo
   return s;
 }
 
+// ---- catch-up (row f-10).  One call of n leaves (mbytes of them) in `replies`
+// replies with `entries` proof entries in all.  No buffer of its own: the
+// leaves, offsets and old entries stage where the extend's do, the reply ends
+// and proof offsets (mv_words: ends, then offsets), the target root
+// (mv_roots), the proof entries (mv_proofs, never empty) and the outputs
+// (mv_out: the reply roots if wanted, then the statuses) where the verify
+// forms' do.  The lanes read the leaf and node hashes, so they are kept
+// whether wanted or not: staged (host form), in the fold scratch (device form
+// without a buffer for them).  The passes write the new tree's entries, which
+// no catch-up output takes: they go to the front of mk_fnodeh in both forms.
+constexpr uint64_t kCatchupNewBytes = 32 * kMerkleMaxHashes;
+inline MerkleSizes merkle_catchup_needs(uint64_t old_size, uint64_t n, uint64_t mbytes, uint64_t replies,
+                                        uint64_t entries, bool host_form, bool want_leaf, bool want_node,
+                                        bool want_roots) {
+  const uint64_t nodes = merkle_node_count(old_size + n) - merkle_node_count(old_size);
+  MerkleSizes s = {};
+  s[mk_roots] = 32 * merkle_scratch_hashes(old_size, old_size + n);
+  s[mk_fnodeh] = kCatchupNewBytes + (!host_form && !want_node ? 32 * nodes : 0);
+  if (host_form) {
+    s[mk_leaves] = mbytes + 64;
+    s[mk_off] = 8 * (n + 1);
+    s[mk_hashes] = kMerkleHashesBytes;
+    s[mk_leafh] = 32 * n;
+    s[mk_nodeh] = 32 * nodes;
+    s[mv_words] = 8 * (2 * replies + 1);
+    s[mv_roots] = 32;
+    s[mv_proofs] = entries ? 32 * entries : 32;
+    s[mv_out] = (want_roots ? 32 * replies : 0) + replies;
+  } else {
+    s[mk_fleafh] = want_leaf ? 0 : 32 * n;
+  }
+  return s;
+}
+
 }  // namespace edv

@@ -68,5 +68,9 @@ struct MerkleAuditNodes;
 struct MerkleAuditLeaves;
 hipError_t launch_merkle_audit_nodes_kernel(hipStream_t s, const MerkleAuditNodes& a, uint64_t* summary);
 hipError_t launch_merkle_audit_leaves_kernel(hipStream_t s, const MerkleAuditLeaves& a, uint64_t* summary);
+// catch-up (MerkleCatchup: edv_merkle.h), one lane per reply, after the passes
+// on the same stream; no launch for replies = 0
+struct MerkleCatchup;
+hipError_t launch_merkle_catchup_kernel(hipStream_t s, const MerkleCatchup& a);
 
 }  // namespace edv

@@ -5,7 +5,8 @@
 // this file; ledger/merkle_verifier.py MerkleVerifier), and the making of them
 // from the stored hashes (row f-8, after it; CompactMerkleTree.inclusion_proof
 // / consistency_proof / merkle_tree_hash(0, n)), and the auditing of those
-// stored hashes, entry by entry (row f-9, at the very end).
+// stored hashes, entry by entry (row f-9, after that), and the verifying and
+// applying of catch-up replies in one call (row f-10, at the very end).
 //
 // Replaces, per batch of transactions:
 //   ledger/ledger.py:145-148              Ledger._addToTree (one append per txn)
@@ -396,27 +397,32 @@ EDV_HD void merkle_copy_hash(uint32_t* dst, const uint32_t* src) {  // both 16-b
   for (int w = 0; w < 8; w++) dst[w] = src[w];
 #endif
 }
-// Leaf i of the call, i < a.n: the root of the tree after it (merkle_fold's
-// order over the entries of hashes(s): from the lowest set bit up) and its
-// audit path (the entries of hashes(s - 1), lowest bit first, at entry
+// The root of the tree of s leaves inside the call, 1 <= s, a.old_size <= s <=
+// a.old_size + a.n: merkle_fold's order over the entries of hashes(s), from the
+// lowest set bit up.
+EDV_HD void merkle_fold_entries(uint32_t acc[8], const MerkleAppend& a, uint64_t s) {
+  uint64_t bits = s;
+  int b = __builtin_ctzll(bits);
+  merkle_load_hash(acc, merkle_entry(a, s, b));
+  bits &= bits - 1;
+#pragma unroll 1
+  while (bits) {
+    b = __builtin_ctzll(bits);
+    bits &= bits - 1;
+    uint32_t l[8], r[8];
+    merkle_load_hash(l, merkle_entry(a, s, b));
+    for (int w = 0; w < 8; w++) r[w] = acc[w];
+    merkle_node_hash(acc, l, r);
+  }
+}
+// Leaf i of the call, i < a.n: the root of the tree after it (merkle_fold_entries)
+// and its audit path (the entries of hashes(s - 1), lowest bit first, at entry
 // P(old + i) - P(old) of the packed output).
 EDV_HD void merkle_append_leaf(const MerkleAppend& a, uint64_t i) {
   const uint64_t s = a.old_size + i + 1;
   if (a.roots) {
-    uint64_t bits = s;
-    int b = __builtin_ctzll(bits);
     uint32_t acc[8];
-    merkle_load_hash(acc, merkle_entry(a, s, b));
-    bits &= bits - 1;
-#pragma unroll 1
-    while (bits) {
-      b = __builtin_ctzll(bits);
-      bits &= bits - 1;
-      uint32_t l[8], r[8];
-      merkle_load_hash(l, merkle_entry(a, s, b));
-      for (int w = 0; w < 8; w++) r[w] = acc[w];
-      merkle_node_hash(acc, l, r);
-    }
+    merkle_fold_entries(acc, a, s);
     merkle_store_hash(a.roots + 8 * i, acc);
   }
   if (a.paths) {
@@ -1021,6 +1027,63 @@ inline void merkle_audit_run(const Args& a, uint64_t count, uint64_t first_pos, 
     summary[0]++;
     if (first_pos + i < summary[1]) summary[1] = first_pos + i;
   }
+}
+
+// ---- catch-up (row f-10: what plenum/common/ledger_manager.py:505-609
+// hasValidCatchupReplies / _add_txn do one reply at a time).  The call's n
+// leaves are the transactions of `replies` replies in order: reply k ends at
+// leaf reply_end[k] of the call (ends never fall; an empty reply repeats the
+// end before it) and carries a consistency proof from the tree at its end,
+// s = old_size + reply_end[k], to the catch-up target (final_size,
+// final_root).  One lane per reply, after the extend's passes: the root of the
+// tree of s leaves is a fold of hashes(s), every entry of which the old tree
+// or the passes have (merkle_entry), so a transaction is hashed once and the
+// replies' proofs are walked side by side.  The status is the walk's; RANGE
+// also where the arrays do not describe the call (an end past n).
+struct MerkleCatchup {
+  MerkleAppend t;             // old_size, n and the three sources of merkle_entry; roots / paths unused
+  uint64_t replies, final_size;
+  const uint64_t* reply_end;  // leaves of the call in replies 0 .. k
+  const uint32_t* final_root;
+  const uint32_t* proofs;     // proof k: entries [proof_off[k], proof_off[k + 1]) - proof_base
+  const uint64_t* proof_off;
+  uint64_t proof_base;
+  uint32_t* reply_roots;      // the root at reply k's end at 8 k, zeros where RANGE; or null
+  uint8_t* status;
+};
+// ... from the call's arguments (host side; hashes at any pointer type)
+inline MerkleCatchup merkle_catchup_args(uint64_t old_size, uint64_t n, const void* old_hashes, const void* leaf_hashes,
+                                         const void* node_hashes, const uint64_t* reply_end, uint64_t replies,
+                                         uint64_t final_size, const void* final_root, const void* proofs,
+                                         const uint64_t* proof_off, uint64_t proof_base, void* reply_roots,
+                                         uint8_t* status) {
+  using H = const uint32_t*;
+  return {{old_size, n, 0, H(old_hashes), H(leaf_hashes), H(node_hashes), nullptr, nullptr},
+          replies, final_size, reply_end, H(final_root), H(proofs), proof_off, proof_base,
+          static_cast<uint32_t*>(reply_roots), status};
+}
+// Lane k < a.replies.  The end is checked against n before it is added to
+// old_size (old_size + n <= 2^62: no wrap below that); an end or a size out of
+// range reads neither offsets nor hashes.
+EDV_HD void merkle_catchup_lane(const MerkleCatchup& a, uint64_t k) {
+  const uint64_t e = a.reply_end[k];
+  uint32_t root[8];
+  uint8_t st = kProofRange;
+  if (e <= a.t.n && a.t.old_size + e <= a.final_size) {
+    const uint64_t s = a.t.old_size + e;
+    if (s == 0)
+      merkle_empty_hash(root);
+    else
+      merkle_fold_entries(root, a.t, s);
+    const uint64_t p0 = a.proof_off[k], p1 = a.proof_off[k + 1];
+    uint32_t target[8], oldr[8], newr[8];
+    bool walked;
+    merkle_load_hash(target, a.final_root);
+    st = merkle_verify_consistency_one(oldr, newr, &walked, s, a.final_size, root, target,
+                                       a.proofs + 8 * (p0 - a.proof_base), p1 - p0);
+  }
+  a.status[k] = st;
+  if (a.reply_roots) merkle_store_hash_or_zero(a.reply_roots + 8 * k, root, st != kProofRange);
 }
 
 }  // namespace edv

@@ -8,6 +8,7 @@
 // launches on one stream.  The batched append (row f-6) adds one kernel after
 // them: one lane per new leaf, the root after it and its audit path.  Proof
 // verification (row f-7) is two kernels of the same shape: one lane per proof.
+// Catch-up (row f-10) is one more after the passes: one lane per reply.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -125,6 +126,17 @@ __global__ __launch_bounds__(kMerkleAppendLanes) void edv_merkle_audit_leaves_ke
   merkle_audit_reduce(bad, a.leaf_lo + i0, summary);
 }
 
+// Row f-10: one lane per catch-up reply folds the root of the tree at the
+// reply's end out of the hashes the passes before it on the stream have
+// written and walks the reply's consistency proof to the target
+// (merkle_catchup_lane).  The append and verify kernels' shape: no LDS, no
+// lane talks to another; lanes of a wave differ in trip count through
+// popcount(s) and the proof's length and rejoin at the status store.
+__global__ __launch_bounds__(kMerkleAppendLanes) void edv_merkle_catchup_kernel(MerkleCatchup a) {
+  const uint64_t k = uint64_t(blockIdx.x) * kMerkleAppendLanes + threadIdx.x;
+  if (k < a.replies) merkle_catchup_lane(a, k);
+}
+
 }  // namespace
 
 namespace edv {
@@ -152,6 +164,13 @@ hipError_t launch_merkle_append_kernel(hipStream_t s, const MerkleAppend& a) {
   if (a.n == 0 || (!a.roots && !a.paths)) return hipSuccess;
   const uint64_t blocks = (a.n + kMerkleAppendLanes - 1) / kMerkleAppendLanes;
   edv_merkle_append_kernel<<<dim3(unsigned(blocks)), dim3(kMerkleAppendLanes), 0, s>>>(a);
+  return hipGetLastError();
+}
+
+hipError_t launch_merkle_catchup_kernel(hipStream_t s, const MerkleCatchup& a) {
+  if (a.replies == 0) return hipSuccess;
+  const uint64_t blocks = (a.replies + kMerkleAppendLanes - 1) / kMerkleAppendLanes;
+  edv_merkle_catchup_kernel<<<dim3(unsigned(blocks)), dim3(kMerkleAppendLanes), 0, s>>>(a);
   return hipGetLastError();
 }
 

@@ -1576,6 +1576,73 @@ int run_merkle_hashed_host(DevCtx& c, uint64_t old_size, const uint8_t* old_hash
   return 0;
 }
 
+// ---- catch-up (edv_merkle.h, row f-10).  launch_merkle's passes over the n
+// leaves, then one lane per reply on the same stream, ordered on the scratch by
+// the same event.  `a` comes from merkle_catchup_args with the caller's leaf
+// and node hash buffers (null: the fold scratch takes them, merkle_catchup_needs'
+// device form); the new tree's entries, which the passes write and nothing
+// reads, go to the front of mk_fnodeh.  Caller holds c.mu.
+int launch_merkle_catchup(DevCtx& c, MerkleCatchup a, const uint8_t* d_leaves, const uint64_t* d_off, uint64_t leaf_base,
+                          hipStream_t s) {
+  MerkleBufs& m = c.mk;
+  const uint64_t old_size = a.t.old_size, n = a.t.n, new_size = old_size + n;
+  if (!m.done) HIPOK(hipEventCreateWithFlags(&m.done, hipEventDisableTiming), "event");
+  const MerkleSizes need = merkle_catchup_needs(old_size, n, 0, a.replies, 0, false, a.t.leaf_hashes, a.t.node_hashes, false);
+  if (const int err = m.ensure(need)) return err;
+  HIPOK(hipStreamWaitEvent(s, m.done, 0), "wait merkle scratch");
+  if (need[mk_fleafh]) a.t.leaf_hashes = m.at<uint32_t>(mk_fleafh);
+  if (need[mk_fnodeh] > kCatchupNewBytes) a.t.node_hashes = m.at<uint32_t>(mk_fnodeh) + kCatchupNewBytes / 4;
+  MerklePass p = merkle_pass_args(old_size, new_size, a.t.old_hashes, const_cast<uint32_t*>(a.t.leaf_hashes),
+                                  const_cast<uint32_t*>(a.t.node_hashes), m.at(mk_fnodeh));
+  HIPOK(merkle_for_each_pass(old_size, new_size, m.at<uint32_t>(mk_roots), p,
+                             [&](const MerklePass& q) { return launch_merkle_pass_kernel(s, q, d_leaves, d_off, leaf_base); }),
+        "merkle pass launch");
+  HIPOK(launch_merkle_catchup_kernel(s, a), "merkle catchup launch");
+  HIPOK(hipEventRecord(m.done, s), "record merkle scratch");
+  return 0;
+}
+
+// The host form: the leaves staged as run_merkle_host stages them, the reply
+// ends, proof offsets, target root and proof entries as the verify forms stage
+// theirs (merkle_catchup_needs); copies back the statuses and the outputs asked
+// for.  Caller holds c.mu and has checked the arguments; replies > 0.
+int run_merkle_catchup_host(DevCtx& c, uint64_t old_size, const uint8_t* old_hashes, const uint8_t* leaves,
+                            const uint64_t* off, uint64_t n, const uint64_t* reply_end, uint64_t replies,
+                            uint64_t final_size, const uint8_t* final_root, const uint8_t* proofs,
+                            const uint64_t* proof_off, uint8_t* leaf_hashes, uint8_t* node_hashes, uint8_t* reply_roots,
+                            uint8_t* status) {
+  MerkleBufs& m = c.mk;
+  const uint64_t nodes = merkle_node_count(old_size + n) - merkle_node_count(old_size);
+  const uint64_t nold = uint64_t(popc64(old_size));
+  const uint64_t mbase = n ? off[0] : 0, mbytes = n ? off[n] - off[0] : 0;
+  const MerkleSizes need = merkle_catchup_needs(old_size, n, mbytes, replies, proof_off[replies] - proof_off[0], true,
+                                                leaf_hashes, node_hashes, reply_roots);
+  if (const int err = m.ensure(need)) return err;
+  const hipStream_t s = c.stream;
+  if (mbytes) HIPOK(hipMemcpyAsync(m.at(mk_leaves), leaves + mbase, mbytes, hipMemcpyHostToDevice, s), "h2d leaves");
+  if (n) HIPOK(hipMemcpyAsync(m.at(mk_off), off, (n + 1) * 8, hipMemcpyHostToDevice, s), "h2d leaf_off");
+  if (nold) HIPOK(hipMemcpyAsync(m.at(mk_hashes), old_hashes, 32 * nold, hipMemcpyHostToDevice, s), "h2d old hashes");
+  HIPOK(hipMemcpyAsync(m.at(mv_roots), final_root, 32, hipMemcpyHostToDevice, s), "h2d final root");
+  if (const int err = stage_proofs(c, proofs, proof_off, replies)) return err;
+  WordStage w{m.at<uint64_t>(mv_words), s};
+  const uint64_t *d_end = w.put(reply_end, replies), *d_poff = w.put(proof_off, replies + 1);
+  HIPOK(w.e, "h2d reply words");
+  uint8_t *d_leafh = m.at(mk_leafh, need), *d_nodeh = m.at(mk_nodeh, need);
+  uint8_t* d_rroots = reply_roots ? m.at(mv_out) : nullptr;
+  uint8_t* d_status = m.at(mv_out) + (reply_roots ? 32 * replies : 0);
+  if (const int err = launch_merkle_catchup(
+          c, merkle_catchup_args(old_size, n, m.at(mk_hashes), d_leafh, d_nodeh, d_end, replies, final_size,
+                                 m.at(mv_roots), m.at(mv_proofs), d_poff, proof_off[0], d_rroots, d_status),
+          m.at(mk_leaves), m.at<uint64_t>(mk_off), mbase, s))
+    return err;
+  HIPOK(hipMemcpyAsync(status, d_status, replies, hipMemcpyDeviceToHost, s), "d2h reply status");
+  if (reply_roots) HIPOK(hipMemcpyAsync(reply_roots, d_rroots, 32 * replies, hipMemcpyDeviceToHost, s), "d2h reply roots");
+  if (leaf_hashes && n) HIPOK(hipMemcpyAsync(leaf_hashes, d_leafh, 32 * n, hipMemcpyDeviceToHost, s), "d2h leaf hashes");
+  if (node_hashes && nodes) HIPOK(hipMemcpyAsync(node_hashes, d_nodeh, 32 * nodes, hipMemcpyDeviceToHost, s), "d2h node hashes");
+  HIPOK(hipStreamSynchronize(s), "stream sync");
+  return 0;
+}
+
 // Asynchronous host path.  Wait for a slot's batch and hand over its verdicts.
 void async_fail(DevCtx& c, DevCtx::AsyncSlot& s) {
   c.ledger.fail(s.ticket);
@@ -2757,6 +2824,78 @@ int edv_merkle_extend_hashed_dev(uint64_t old_size, const uint8_t* d_old_hashes,
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : cl.c->stream;
   if ((err = launch_merkle(*cl.c, old_size, d_old_hashes, nullptr, nullptr, 0, n, nullptr, d_node_hashes, d_new_hashes,
                            d_root, s, nullptr, nullptr, n ? d_leaf_hashes : nullptr)))
+    return err;
+  if (!stream) HIPOK(hipStreamSynchronize(s), "stream sync");
+  return 0;
+}
+
+// Catch-up (row f-10).  What both forms check of the sizes and of the pointers
+// every call needs; d: "d_" for the device form's names in the messages.
+static int check_catchup_args(uint64_t old_size, uint64_t n, uint64_t replies, const void* old_hashes,
+                              const void* reply_end, const void* final_root, const void* proof_off, const void* status,
+                              const std::string& d) {
+  if (n > EDV_MERKLE_MAX_LEAVES) return set_err(EDV_E_ARG, "merkle: more than EDV_MERKLE_MAX_LEAVES leaves");
+  if (old_size > kMerkleMaxSize || old_size + n > kMerkleMaxSize) return set_err(EDV_E_ARG, "merkle: tree size above 2^62");
+  if (old_size && !old_hashes) return set_err(EDV_E_ARG, ("merkle: null " + d + "old_hashes").c_str());
+  if (!reply_end || !final_root || !proof_off || !status)
+    return set_err(EDV_E_ARG, ("merkle catchup: null " + d + "reply_end / " + d + "final_root / " + d + "proof_off / " +
+                               d + "status").c_str());
+  if (replies == 0 && n) return set_err(EDV_E_ARG, "merkle catchup: leaves without a reply");
+  if (replies > n + 1) return set_err(EDV_E_ARG, "merkle catchup: more than n + 1 replies");
+  return 0;
+}
+
+int edv_merkle_catchup(uint64_t old_size, const uint8_t* old_hashes, const uint8_t* leaves, const uint64_t* leaf_off,
+                       uint64_t n, const uint64_t* reply_end, uint64_t replies, uint64_t final_size,
+                       const uint8_t* final_root, const uint8_t* proofs, const uint64_t* proof_off, uint8_t* leaf_hashes,
+                       uint8_t* node_hashes, uint8_t* reply_roots, uint8_t* status, int device) {
+  g_err.clear();
+  int err;
+  if ((err = check_catchup_args(old_size, n, replies, old_hashes, reply_end, final_root, proof_off, status, ""))) return err;
+  if (n) {
+    if (!leaf_off) return set_err(EDV_E_ARG, "merkle: null leaf_off");
+    if ((err = check_offsets(leaf_off, n))) return err;
+    if (!leaves && leaf_off[n] != leaf_off[0]) return set_err(EDV_E_ARG, "merkle: null leaves");
+  }
+  if (replies == 0) return 0;
+  for (uint64_t k = 1; k < replies; k++)
+    if (reply_end[k] < reply_end[k - 1]) return set_err(EDV_E_ARG, "merkle catchup: reply_end not non-decreasing");
+  if (reply_end[replies - 1] != n) return set_err(EDV_E_ARG, "merkle catchup: the last reply does not end at n");
+  for (uint64_t k = 0; k < replies; k++)
+    if (proof_off[k + 1] < proof_off[k]) return set_err(EDV_E_ARG, "merkle catchup: proof_off not non-decreasing");
+  if (!proofs && proof_off[replies] != proof_off[0]) return set_err(EDV_E_ARG, "merkle catchup: null proofs");
+  CtxLock cl(device);
+  if (cl.err) return cl.err;
+  memset(status, EDV_PROOF_UNVERIFIED, replies);  // a call that fails part-way leaves rejections
+  return run_merkle_catchup_host(*cl.c, old_size, old_hashes, leaves, leaf_off, n, reply_end, replies, final_size,
+                                 final_root, proofs, proof_off, leaf_hashes, node_hashes, reply_roots, status);
+}
+
+int edv_merkle_catchup_dev(uint64_t old_size, const uint8_t* d_old_hashes, const uint8_t* d_leaves,
+                           const uint64_t* d_leaf_off, uint64_t leaf_base, uint64_t n, const uint64_t* d_reply_end,
+                           uint64_t replies, uint64_t final_size, const uint8_t* d_final_root, const uint8_t* d_proofs,
+                           const uint64_t* d_proof_off, uint64_t proof_base, uint8_t* d_leaf_hashes,
+                           uint8_t* d_node_hashes, uint8_t* d_reply_roots, uint8_t* d_status, int device, void* stream) {
+  g_err.clear();
+  int err;
+  if ((err = check_catchup_args(old_size, n, replies, d_old_hashes, d_reply_end, d_final_root, d_proof_off, d_status, "d_")))
+    return err;
+  if (n && (!d_leaves || !d_leaf_off)) return set_err(EDV_E_ARG, "merkle: null d_leaves / d_leaf_off");
+  // before anything reaches the GPU: the kernels read ends and offsets as 64-bit
+  // words and read and store every hash as two 16-byte vectors
+  for (const uint64_t* p : {d_leaf_off, d_reply_end, d_proof_off})
+    if (reinterpret_cast<uintptr_t>(p) & 7) return set_err(EDV_E_ARG, "merkle catchup: 64-bit arrays must be 8-byte aligned");
+  for (const uint8_t* p : {d_old_hashes, d_final_root, d_proofs, static_cast<const uint8_t*>(d_leaf_hashes),
+                           static_cast<const uint8_t*>(d_node_hashes), static_cast<const uint8_t*>(d_reply_roots)})
+    if (reinterpret_cast<uintptr_t>(p) & 15) return set_err(EDV_E_ARG, "merkle: hash buffers must be 16-byte aligned");
+  if (replies == 0) return 0;
+  CtxLock cl(device);
+  if (cl.err) return cl.err;
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : cl.c->stream;
+  if ((err = launch_merkle_catchup(
+           *cl.c, merkle_catchup_args(old_size, n, d_old_hashes, d_leaf_hashes, d_node_hashes, d_reply_end, replies,
+                                      final_size, d_final_root, d_proofs, d_proof_off, proof_base, d_reply_roots, d_status),
+           d_leaves, d_leaf_off, leaf_base, s)))
     return err;
   if (!stream) HIPOK(hipStreamSynchronize(s), "stream sync");
   return 0;

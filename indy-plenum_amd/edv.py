@@ -126,6 +126,11 @@ def lib():
         for f in (h.edv_merkle_audit_nodes, h.edv_merkle_audit_nodes_dev, h.edv_merkle_audit_leaves,
                   h.edv_merkle_audit_leaves_dev, h.edv_merkle_extend_hashed, h.edv_merkle_extend_hashed_dev):
             f.restype = ctypes.c_int
+        h.edv_merkle_catchup.argtypes = [u64, vp, vp, vp, u64, vp, u64, u64, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int]
+        h.edv_merkle_catchup.restype = ctypes.c_int
+        h.edv_merkle_catchup_dev.argtypes = [u64, vp, vp, vp, u64, u64, vp, u64, u64, vp, vp, vp, u64, vp, vp, vp, vp,
+                                             ctypes.c_int, vp]
+        h.edv_merkle_catchup_dev.restype = ctypes.c_int
         h.edv_verify_batch_dev_flags.argtypes = [vp, vp, vp, vp, u64, u64, vp, ctypes.c_int, vp, ctypes.c_uint32]
         h.edv_verify_batch_dev_flags.restype = ctypes.c_int
         h.edv_verify_batch_dev_pipelined.argtypes = [vp, vp, vp, vp, u64, u64, vp, ctypes.c_int, ctypes.c_uint32]
@@ -911,6 +916,44 @@ def merkle_extend_hashed_device(old_size, d_old_hashes, d_leaf_hashes, n, d_node
     """Device-resident form (pointers are ints, None = NULL); async on `stream` if given."""
     _check(lib().edv_merkle_extend_hashed_dev(old_size, d_old_hashes, d_leaf_hashes, n, d_node_hashes, d_new_hashes,
                                               d_root, device, stream))
+
+
+# catch-up (row f-10)
+def merkle_catchup(old_size: int, old_hashes, leaves, offsets, reply_end, final_size: int, final_root, proofs,
+                   proof_off, want_leaf_hashes=True, want_node_hashes=True, want_roots=True, device: int = 0):
+    """Verify and hash the replies of a catch-up in one call (edv_merkle_catchup,
+    row f-10).  The n leaves (leaves / offsets as for merkle_extend) are the
+    transactions of len(reply_end) in-order replies: reply k ends at leaf
+    reply_end[k] of the call and carries the consistency proof k (proofs /
+    proof_off as for merkle_verify_consistency) from the tree at its end to
+    (final_size, final_root).  Returns (leaf_hashes, node_hashes, reply_roots,
+    status): the first two as merkle_extend's, reply_roots the (replies, 32)
+    tree heads at the replies' ends, status one PROOF_* per reply; outputs not
+    wanted are None.  A status after the first failure is computed over
+    rejected transactions."""
+    final_size = int(final_size)
+    if not 0 <= final_size < 1 << 64:
+        raise ValueError("final_size out of range")
+    old_size, n, head, _keep, leaf_h, node_h, _, _ = _merkle_call(old_size, old_hashes, leaves, offsets,
+                                                                  want_leaf_hashes, want_node_hashes)
+    poff, replies, proofs = _proof_offsets(proof_off, proofs)
+    ends = _u64(reply_end, "reply_end", replies)
+    final_root = _u8(final_root, "final_root", 32)
+    roots = np.zeros((replies, 32), dtype=np.uint8) if want_roots else None
+    status = np.zeros(replies, dtype=np.uint8)
+    _check(lib().edv_merkle_catchup(*head, ends.ctypes.data, replies, final_size, final_root.ctypes.data,
+                                    proofs.ctypes.data, poff.ctypes.data, _ptr(leaf_h), _ptr(node_h), _ptr(roots),
+                                    status.ctypes.data, device))
+    return leaf_h, node_h, roots, status
+
+
+def merkle_catchup_device(old_size, d_old_hashes, d_leaves, d_off, n, d_reply_end, replies, final_size, d_final_root,
+                          d_proofs, d_proof_off, d_leaf_hashes, d_node_hashes, d_reply_roots, d_status, device=0,
+                          leaf_base=0, proof_base=0, stream=None):
+    """Device-resident form (pointers are ints, None = NULL); async on `stream` if given."""
+    _check(lib().edv_merkle_catchup_dev(old_size, d_old_hashes, d_leaves, d_off, leaf_base, n, d_reply_end, replies,
+                                        final_size, d_final_root, d_proofs, d_proof_off, proof_base, d_leaf_hashes,
+                                        d_node_hashes, d_reply_roots, d_status, device, stream))
 
 
 def verify_detached_batch(items, device_mask: int = 0):

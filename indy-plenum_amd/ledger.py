@@ -16,10 +16,17 @@ classes, written from their semantics:
   plenum/common/ledger_manager.py:995-998 a consistency proof and both roots -> consistency_proofs (row f-8)
   ledger/ledger.py:70-114                 recoverTree trusts a store that has leaves -> auditHashStore,
                                           recoverTreeVerified (row f-9)
+  plenum/common/ledger_manager.py:505-609 per reply hasValidCatchupReplies, then _add_txn -> ledger.add per
+                                          transaction -> applyCatchupReplies, one call per pass (row f-10)
 
 commitTxns(count) is one CompactMerkleTree.append_batch call
 (edv_merkle_append_batch from merkle.MIN_DEVICE_APPEND_LEAVES transactions
 on): every committed transaction still gets its own rootHash and auditPath.
+applyCatchupReplies(replies, final_size, final_root_hash) is one
+CompactMerkleTree.extend_verified call for a pass of in-order catch-up
+replies (edv_merkle_catchup from merkle.MIN_DEVICE_CATCHUP_LEAVES transactions
+on): the leading replies whose consistency proofs verify are committed, each
+transaction hashed once, and a merkle.CatchupResult says which they were.
 The transaction log is a list in memory; it holds each transaction as it was
 when it was hashed, a copy taken before the committed transaction is updated
 with its Merkle info (the reference logs the serialization made before the
@@ -299,6 +306,28 @@ class Ledger:
                 [_as_hash(p) for p in proof]))
         except Exception:
             return False
+
+    def applyCatchupReplies(self, replies, final_size, final_root_hash):
+        """Verify and commit in-order catch-up replies in one pass (row f-10;
+        plenum/common/ledger_manager.py:505-609 checks one reply at a time with
+        a temporary tree and then adds its transactions one by one, hashing
+        each twice).  replies: a list of (txns, proof), the transactions in
+        seqNo order from size + 1 on, each reply's consistency proof leading
+        from the tree at its end to the one of final_size leaves and
+        final_root_hash; hashes are base58 strings or bytes, as in
+        verify_catchup_txns.  One CompactMerkleTree.extend_verified call
+        (edv_merkle_catchup from merkle.MIN_DEVICE_CATCHUP_LEAVES transactions
+        on): every transaction is hashed once.  The log, seqNo and the tree
+        advance by the leading replies that verify, as the reference's loop
+        accepts them; returns the merkle.CatchupResult."""
+        replies = [(list(txns), [_as_hash(p) for p in proof]) for txns, proof in replies]
+        result = self.tree.extend_verified([[self.serialize_for_tree(t) for t in txns] for txns, _ in replies],
+                                           int(final_size), _as_hash(final_root_hash), [p for _, p in replies],
+                                           on_device=self.on_device, device=self.device)
+        for txns, _ in replies[:result.accepted]:
+            self._transactionLog.extend(copy(t) for t in txns)
+        self.seqNo += result.accepted_leaves
+        return result
 
     def reset_uncommitted(self):
         self.uncommittedTxns = []

@@ -46,6 +46,16 @@ consistency proofs in one edv_merkle_verify_inclusion /
 edv_merkle_verify_consistency call, one lane per proof, returning a
 ProofVerdicts.  `verify_append_batch` hands an AppendBatch's packed paths and
 roots to the device as they are.
+
+`extend_verified` (row f-10; plenum/common/ledger_manager.py:505-609, where a
+joining node builds a temporary tree per catch-up reply, walks one consistency
+proof from it and then appends the reply's transactions one by one) takes the
+transactions of a whole pass of in-order replies with their proofs: one
+edv_merkle_catchup call hashes every transaction once (the extend's kernels)
+and checks every reply's proof against the tree at its end (kernel
+edv_merkle_catchup_kernel, one lane per reply); the longest verified prefix is
+applied from the call's own outputs and a CatchupResult says which replies
+that was.
 """
 import hashlib
 from binascii import hexlify
@@ -98,6 +108,20 @@ MIN_DEVICE_PROVE_PROOFS = 16
 # nodes the node store alone wins, 49.3 us against 61.1 us, and with the 66
 # leaves the loop does, 93.7 us against 134.5 us; at 16 the loop wins both)
 MIN_DEVICE_AUDIT_ENTRIES = 256
+
+
+# extend_verified / Ledger.applyCatchupReplies(on_device=None) take the device
+# from this many leaves in all on: the smallest measured total at which the one
+# device call beats, on both trees and beyond the rows' spread, both the loop it
+# replaces and the same pass on the host (profiles/r12/merkle_catchup_bench.json,
+# "crossover": at 1,024 transactions of 256 bytes in replies of 100, 679 us
+# (600-1,121) against 1,309 us (1,133-1,814) on the host and 8.9 ms for the
+# loop onto an empty tree, 740 us against 1,200 us and 10.4 ms onto 2^20 +
+# 12,345 leaves; at 256 the host pass wins on the larger tree, 292 us against
+# 471 us, and is level on the empty one, 336 us against 351 us; against the
+# loop alone the device call wins at every size measured, 64 included;
+# nothing between 256 and 1,024 was measured)
+MIN_DEVICE_CATCHUP_LEAVES = 1024
 
 
 class ConsistencyVerificationFailed(Exception):
@@ -421,6 +445,64 @@ class StoreAudit:
                                  self.counts_ok, self.frontier_ok)
 
 
+class CatchupResult:
+    """What extend_verified / Ledger.applyCatchupReplies did with the replies
+    of a catch-up: `status`, a uint8 array of edv.PROOF_* (one per reply; 0,
+    PROOF_UNVERIFIED, for a reply of a call that was not made any more);
+    `roots`, an (r, 32) uint8 array, the tree head at each reply's end (zeros
+    where the status is PROOF_RANGE or PROOF_UNVERIFIED); `accepted`, the
+    number of leading PROOF_OK replies, which are the ones that were applied;
+    `accepted_leaves`, the leaves in them.
+
+    A status after the first failure is computed over the rejected
+    transactions (the tree at that reply's end contains them) and is not a
+    judgement of that reply: send the rest again once the failing reply is
+    replaced."""
+
+    def __init__(self, status, roots, accepted, accepted_leaves):
+        self.status = np.asarray(status, dtype=np.uint8)
+        self.roots = roots
+        self.accepted = accepted
+        self.accepted_leaves = accepted_leaves
+
+    @property
+    def ok(self):
+        """Was every reply applied?"""
+        return self.accepted == len(self.status)
+
+    def __len__(self):
+        return len(self.status)
+
+    def __repr__(self):
+        return "CatchupResult(accepted=%d of %d replies, accepted_leaves=%d, status=%r)" % (
+            self.accepted, len(self.status), self.accepted_leaves, self.status.tolist())
+
+
+def _leading_ok(status):
+    bad = np.flatnonzero(np.asarray(status) != edv.PROOF_OK)
+    return int(bad[0]) if len(bad) else len(status)
+
+
+def _call_frontier(old_size, old_hashes, size, leaf_h, node_h):
+    """hashes(size), largest first, out of one call's outputs, old_size <= size
+    <= old_size + len(leaf_h): merkle_entry's rule (edv_merkle.h).  The entry
+    for set bit b is block k = (size >> b) - 1 at height b; if it ends at or
+    before old_size it is the old tree's entry for the same bit, else the call
+    made it: a leaf hash (b = 0) or the node at its node-store position."""
+    base, out = old_size - _popcount(old_size), []
+    for b in reversed(range(size.bit_length())):
+        if not (size >> b) & 1:
+            continue
+        k = (size >> b) - 1
+        if ((k + 1) << b) <= old_size:
+            out.append(bytes(old_hashes[_popcount(old_size >> (b + 1))]))
+        elif b == 0:
+            out.append(leaf_h[k - old_size].tobytes())
+        else:
+            out.append(node_h[node_position(b, k) - 1 - base].tobytes())
+    return out
+
+
 def _carry_chain(hasher, size, stack, leaf_hashes):
     """The appends' carry chain over leaf hashes: (size, stack, node hashes in store order)."""
     nodes = []
@@ -620,6 +702,111 @@ class CompactMerkleTree:
         new_tree = self.__copy__()
         new_tree.extend(new_leaves, on_device=on_device)
         return new_tree
+
+    # ---- catch-up (row f-10)
+    def extend_verified(self, parts, final_size, final_root, proofs, on_device=None, max_call=None, device=0):
+        """Apply the longest prefix of `parts` (lists of leaves: the
+        transactions of in-order catch-up replies) whose consistency proofs all
+        verify: proofs[k] must lead from the tree at part k's end to the tree
+        of final_size leaves and root final_root.  Tree and hash store end
+        byte-identical to `extend` over the accepted parts' leaves; nothing of a
+        rejected part is written.  Returns a CatchupResult.
+
+        On the device one edv_merkle_catchup call hashes every leaf once and
+        checks the parts' proofs side by side (kernel edv_merkle_catchup_kernel
+        after the extend's); on the host the same work goes part by part.
+        on_device True / False forces the route; None takes the device from
+        MIN_DEVICE_CATCHUP_LEAVES leaves in all on.  Above max_call leaves (at
+        most, and by default, edv.MERKLE_MAX_LEAVES) the calls split at part
+        boundaries, and none is made after one with a failure; a single part
+        above max_call raises ValueError before anything is applied."""
+        parts = [list(p) for p in parts]
+        proofs = [[_hash32(h, "a proof entry") for h in p] for p in proofs]
+        if len(proofs) != len(parts):
+            raise ValueError("one proof per part")
+        final_size, final_root = int(final_size), _hash32(final_root, "final_root")
+        if not _in_u64(final_size):
+            raise ValueError("final_size out of range")
+        total = sum(len(p) for p in parts)
+        if on_device is None:
+            on_device = total >= MIN_DEVICE_CATCHUP_LEAVES
+        if on_device and self.__hasher.hashfunc is not hashlib.sha256:
+            raise ValueError("the device hashes SHA-256 trees only")
+        step = edv.MERKLE_MAX_LEAVES if max_call is None else int(max_call)
+        if step < 1 or step > edv.MERKLE_MAX_LEAVES:
+            raise ValueError("max_call must be in [1, %d]" % edv.MERKLE_MAX_LEAVES)
+        if any(len(p) > step for p in parts):
+            raise ValueError("a part is larger than max_call")
+        if self.__tree_size + total > edv.MERKLE_MAX_SIZE:
+            raise ValueError("tree size above 2^62")
+        r = len(parts)
+        status, roots = np.zeros(r, dtype=np.uint8), np.zeros((r, 32), dtype=np.uint8)
+        accepted = accepted_leaves = lo = 0
+        while lo < r:
+            hi, count = lo + 1, len(parts[lo])
+            while hi < r and count + len(parts[hi]) <= step:
+                count += len(parts[hi])
+                hi += 1
+            call = self._catchup_device if on_device else self._catchup_host
+            st, rt, ok, ok_leaves = call(parts[lo:hi], proofs[lo:hi], final_size, final_root, device)
+            status[lo:hi], roots[lo:hi] = st, rt
+            accepted += ok
+            accepted_leaves += ok_leaves
+            if ok < hi - lo:
+                break
+            lo = hi
+        return CatchupResult(status, roots, accepted, accepted_leaves)
+
+    def _catchup_host(self, parts, proofs, final_size, final_root, device):
+        """One call's parts on the host: (statuses, roots, accepted parts,
+        accepted leaves), the accepted prefix applied.  Parts after a failure
+        are hashed on, as the device call does, and not written."""
+        hasher, store = self.__hasher, self.__hashStore
+        size, stack = self.__tree_size, list(self.__hashes)
+        status, roots, good, ok, ok_leaves = [], [], True, 0, 0
+        for part, proof in zip(parts, proofs):
+            leaf_hashes = [hasher.hash_leaf(leaf) for leaf in part]
+            size, stack, nodes = _carry_chain(hasher, size, stack, leaf_hashes)
+            root = hasher.hash_fold(stack)
+            if size > final_size:
+                st, root = edv.PROOF_RANGE, _ZERO32
+            else:
+                st, _ = _walk_consistency(hasher, size, final_size, root, final_root, proof)
+            status.append(st)
+            roots.append(root)
+            good = good and st == edv.PROOF_OK
+            if good:
+                store.writeLeafs(b"".join(leaf_hashes))
+                store.writeNodes(b"".join(nodes))
+                self._update(size, stack)
+                self.__root_hash = root
+                ok += 1
+                ok_leaves += len(part)
+        return status, np.frombuffer(b"".join(roots), np.uint8).reshape(-1, 32), ok, ok_leaves
+
+    def _catchup_device(self, parts, proofs, final_size, final_root, device):
+        """One edv_merkle_catchup call over `parts`; as _catchup_host.  The
+        accepted size's hashes are read out of the call's own outputs
+        (_call_frontier): a copied tree's store is empty."""
+        leaves = [leaf for part in parts for leaf in part]
+        off = np.zeros(len(leaves) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(x) for x in leaves], dtype=np.uint64)
+        ends = np.cumsum([len(p) for p in parts], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(leaves) + b"\0" * 8, dtype=np.uint8)
+        packed, poff = _pack_proofs(proofs)
+        old_size, old_hashes = self.__tree_size, self.__hashes
+        leaf_h, node_h, roots, status = edv.merkle_catchup(old_size, b"".join(old_hashes), blob, off, ends, final_size,
+                                                           final_root, packed, poff, device=device)
+        ok = _leading_ok(status)
+        ok_leaves = int(ends[ok - 1]) if ok else 0
+        if ok:
+            size = old_size + ok_leaves
+            nodes = edv.merkle_node_span(old_size, ok_leaves)
+            self.__hashStore.writeLeafs(leaf_h[:ok_leaves])
+            self.__hashStore.writeNodes(node_h[:nodes])
+            self._update(size, _call_frontier(old_size, old_hashes, size, leaf_h, node_h))
+            self.__root_hash = roots[ok - 1].tobytes()
+        return status, roots, ok, ok_leaves
 
     # ---- reading (host, from the hash store)
     def merkle_tree_hash(self, start, end):

@@ -71,6 +71,17 @@ over a DeviceHashStore, 10,000 leaves and 2^20 + 12,345:
 and (b) against (e) on stores of 16, 64, 256 and 1,024 nodes, alone and with their leaves, whose smallest size from
 which (b) wins both ways is MIN_DEVICE_AUDIT_ENTRIES.
 
+With --leg catchup: catch-up in one call (row f-10), written to
+profiles/r12/merkle_catchup_bench.json.  A node at old = 0 and at old = 2^20 +
+12,345 receives 64, 256, 1,024 and 10,000 transactions of 256 bytes in replies
+of 100, each with its consistency proof to the pool's tree:
+  b  Ledger.applyCatchupReplies(on_device=True)    one edv_merkle_catchup call for the pass
+  h  Ledger.applyCatchupReplies(on_device=False)   the same pass on the host
+  e  per reply Ledger.verify_catchup_txns, then Ledger.add per transaction: the loop there was before
+The three are timed interleaved; every call starts from a fresh ledger at the
+old tree.  The smallest total from which (b) beats (e) and (h) on both trees
+beyond the rows' spread is MIN_DEVICE_CATCHUP_LEAVES.
+
 Every figure is wall clock around calls that end in a device synchronise (the
 device forms with stream = NULL synchronise the library stream before they
 return), the median of 5 repetitions after a warm-up; a repetition repeats
@@ -614,9 +625,74 @@ def verify_leg(args, rng):
     return res
 
 
+CATCHUP_TOTALS = (64, 256, 1024, 10000)
+CATCHUP_REPLY = 100
+
+
+def catchup_leg(args, rng):
+    """Catch-up in one call against the loop it replaces (module docstring)."""
+    from indy_plenum_amd.ledger import Ledger
+    res = {"leaf_bytes": LEAF_BYTES, "reply_txns": CATCHUP_REPLY, "window_s": args.window, "version": edv.version(),
+           "min_device_catchup_leaves": merkle.MIN_DEVICE_CATCHUP_LEAVES, "rows": [], "crossover": []}
+    top = max(CATCHUP_TOTALS)
+    blob = rng.integers(0, 256, top * LEAF_BYTES, dtype=np.uint8).tobytes()
+    txns = [blob[i * LEAF_BYTES:(i + 1) * LEAF_BYTES] for i in range(top)]
+    for old in OLDS:
+        # the tree the node has (its leaves' content does not matter: 8 bytes each) and the pool's, top leaves on
+        small = rng.integers(0, 256, 8 * old, dtype=np.uint8).tobytes()
+        full = merkle.CompactMerkleTree()
+        full.extend([small[8 * i:8 * i + 8] for i in range(old)], on_device=old > 0, device=args.device)
+        frontier_old = full.hashes
+        full.extend(txns, on_device=True, device=args.device)
+
+        def shell(on_device):
+            led = Ledger(on_device=on_device, device=args.device)
+            led.tree = merkle.CompactMerkleTree(tree_size=old, hashes=frontier_old)
+            led.seqNo = old
+            return led
+        for total in CATCHUP_TOTALS:
+            final = old + total
+            root = full.merkle_tree_hash(0, final)
+            replies = []
+            for lo in range(0, total, CATCHUP_REPLY):
+                hi = min(total, lo + CATCHUP_REPLY)
+                replies.append((txns[lo:hi], full.consistency_proof(old + hi, final) if old + hi < final else []))
+
+            def one_call(on_device):
+                led = shell(on_device)
+                r = led.applyCatchupReplies(replies, final, root)
+                return led, r.accepted
+
+            def loop():
+                led, count = shell(None), 0    # the routing that exists: every temporary tree by its batch size
+                for t, proof in replies:
+                    if not led.verify_catchup_txns(t, final, root, proof):
+                        break
+                    for txn in t:
+                        led.add(txn)
+                    count += 1
+                return led, count
+            for led, count in (one_call(True), one_call(False), loop()):
+                assert count == len(replies) and led.size == final and led.tree.root_hash == root
+            t = timed_interleaved({"b_apply_catchup_replies_device": lambda: one_call(True),
+                                   "h_apply_catchup_replies_host": lambda: one_call(False),
+                                   "e_verify_catchup_txns_and_add_loop": loop}, args.window,
+                                  reps=5 if total < 10000 else 3)
+            row = dict({"old": old, "txns": total, "replies": len(replies)}, **t)
+            res["rows"].append(row)
+            print(json.dumps(row), flush=True)
+    for total in CATCHUP_TOTALS:
+        rows = [r for r in res["rows"] if r["txns"] == total]
+        res["crossover"].append({"txns": total, "device_wins_beyond_spread_on_both_trees": all(
+            r["b_apply_catchup_replies_device"]["max_us"] < min(r["e_verify_catchup_txns_and_add_loop"]["min_us"],
+                                                                r["h_apply_catchup_replies_host"]["min_us"])
+            for r in rows)})
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=("extend", "append", "verify", "prove", "audit"), default="extend")
+    ap.add_argument("--leg", choices=("extend", "append", "verify", "prove", "audit", "catchup"), default="extend")
     ap.add_argument("--out", default=None)
     ap.add_argument("--window", type=float, default=0.2)
     ap.add_argument("--device", type=int, default=0)
@@ -626,12 +702,14 @@ def main():
                     "append": os.path.join(ROOT, "profiles", "r08", "merkle_append_bench.json"),
                     "verify": os.path.join(ROOT, "profiles", "r09", "merkle_verify_bench.json"),
                     "prove": os.path.join(ROOT, "profiles", "r10", "merkle_prove_bench.json"),
-                    "audit": os.path.join(ROOT, "profiles", "r11", "merkle_audit_bench.json")}[args.leg]
+                    "audit": os.path.join(ROOT, "profiles", "r11", "merkle_audit_bench.json"),
+                    "catchup": os.path.join(ROOT, "profiles", "r12", "merkle_catchup_bench.json")}[args.leg]
     if edv.device_count() < 1:
         sys.exit("bench_merkle needs a gfx950 GPU")
     rng = np.random.default_rng(0x6962)
-    if args.leg in ("append", "verify", "prove", "audit"):
-        res = {"append": append_leg, "verify": verify_leg, "prove": prove_leg, "audit": audit_leg}[args.leg](args, rng)
+    if args.leg in ("append", "verify", "prove", "audit", "catchup"):
+        res = {"append": append_leg, "verify": verify_leg, "prove": prove_leg, "audit": audit_leg,
+               "catchup": catchup_leg}[args.leg](args, rng)
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump(res, f, indent=1)
